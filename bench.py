@@ -11,7 +11,13 @@ gateways with json-el conditions over msgpack payloads {"amount", "region", "sco
   3. drain: serialize every record the tick wrote into the exact reference record values + record
      headers, in HBM (zb_serialize) -- the emitted record stream a JNI shim appends to the log.
 The D2H copy of that stream into pinned host memory crosses PCIe; per the task contract it is never
-`value` and is reported beside it (value_pcie_inclusive), measured on one extra step.
+`value` and is reported beside it (value_pcie_inclusive), measured on one extra step (--full).
+
+A plain run sets up, warms up, times --steps steps and prints the line (with the roofline of those steps, from
+their own kernel times). --full adds what takes runs of its own: the CPU baseline (the oracle on a sample of the
+same workload, in processes forked before the GPU is touched), the PCIe-inclusive extra step and, for C3, the
+`extras` lines on the other single-GPU configurations (--no-cpu-baseline / --no-extras drop either from it).
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (dump_outputs).
 
 --config c2 | c3 | c4 | c5 selects another BASELINE configuration (c5: bench_extra.py).
 Multi-GPU (python -m torch.distributed.run ... bench.py --gpus N): one process and one partition per GPU;
@@ -21,7 +27,7 @@ instance index, so every instance's payload is the same whatever the partitionin
 communicate for C1-C4 (weak scaling, no data-path collective; barrier + max-over-ranks timing through
 torch.distributed gloo).
 
-Prints ONE JSON line on rank 0 with "roofline" and "cpu_baseline".
+Prints ONE JSON line on rank 0 with "roofline" (and, under --full, "cpu_baseline", "pcie" and "extras").
 """
 import argparse
 import json
@@ -52,8 +58,14 @@ def parse():
     ap.add_argument("--tasks", type=int, default=20)
     ap.add_argument("--cpu-sample", type=int, default=0, help="instances in the 1-thread oracle sample (0: default)")
     ap.add_argument("--cpu-partitions", type=int, default=0, help="C5: oracle partitions (threads) of the CPU sample (0: 8)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the extra C2 wave-only / C4 lines")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the CPU baseline, the PCIe-inclusive extra step and (C3) the extras lines on "
+                         "the other configurations; a plain run times the --steps steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (step and drain counters, a fixed "
+                         "seeded sample of the drained record stream, checksums of all of it) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full without the extra C2 wave-only / C4 lines")
     ap.add_argument("--no-drain", action="store_true", help="device stepping only (not the contract's step)")
     ap.add_argument("--wave-only", action="store_true", help="force the general wave pipeline (no trajectory path)")
     ap.add_argument("--jobs", choices=("harness", "external", "processor"), default=None,
@@ -74,6 +86,12 @@ def parse():
         a.jobs = "external" if a.config == "c3" else "harness"
     if a.jobs != "harness" and a.config != "c3":
         ap.error("--jobs %s: only C3 (no service task) runs a tick to quiescence without a job processor" % a.jobs)
+    if not a.full:  # a plain run: the timed steps only
+        a.no_cpu_baseline = a.no_extras = True
+    if a.dump_outputs and (a.steady or a.config == "c5"):
+        ap.error("--dump-outputs: the C1-C4 tick (inject, waves, drain) only, not --steady / --config c5")
+    if a.dump_outputs and a.steps < 1:
+        ap.error("--dump-outputs needs a timed step")
     return a
 
 
@@ -129,7 +147,7 @@ def make_engine(cfg, n, a, rank, world, local_rank):
 FRAME_CFG = dict(stream_id=1, raft_term=3, timestamp=1_700_000_000_000)  # (the broker's log stream / raft term)
 
 
-def run_workload(cfg, n, a, rank, world, local_rank, barrier, steps, warmup, drain=True, pcie=False):
+def run_workload(cfg, n, a, rank, world, local_rank, barrier, steps, warmup, drain=True, pcie=False, dump=None):
     xml, pid, blob, offs, jp, desc = workload(cfg, n, rank * n, a.tasks)
     eng = make_engine(cfg, n, a, rank, world, local_rank)
     eng.deploy(xml, 100, 1)
@@ -201,6 +219,8 @@ def run_workload(cfg, n, a, rank, world, local_rank, barrier, steps, warmup, dra
     tot["jobs"] = getattr(a, "jobs", "harness") if cfg == "c3" else "harness"
     tot["desc"] += {"harness": ", canonical job harness", "external": ", ZB_CFG_EXTERNAL_JOBS (the integration's job mode)",
                     "processor": ", ZB_CFG_JOB_PROCESSOR"}[tot["jobs"]] if cfg == "c3" else ""
+    if dump:  # (after the timed region: the last timed step's batch is still in the engine's drain buffers)
+        dump_outputs(dump if world == 1 else os.path.join(dump, "rank%d" % rank), eng, st, ser, frames)
     if pcie and drain:
         tot["pcie"] = pcie_step(eng, n, one_step)
     eng.close()
@@ -229,6 +249,101 @@ def pcie_step(eng, n, one_step, chunk=256 << 20):
             pinned_free(b)
     return {"transitions": st["transitions"], "tick_s": t1 - t0, "d2h_s": t2 - t1, "bytes": ser["value_bytes"],
             "d2h_GBps": ser["value_bytes"] / (t2 - t1) / 1e9 if t2 > t1 else 0.0}
+
+
+# ------------------------------------------------------------------------------ --dump-outputs
+DUMP_SEED = 42
+DUMP_WINDOWS, DUMP_WINDOW = 256, 256  # sampled runs of consecutive records (and the batch's first and last run)
+DUMP_FRAME_WINDOW = 32 << 10          # frames: sampled byte ranges of the frame stream
+DUMP_SAMPLE_BYTES = 10 << 20          # drained bytes kept at most (stored as float32: 40 MiB)
+DUMP_CHUNK = 256 << 20
+STEP_COUNTERS = ("waves", "launches", "records_processed", "records_written", "transitions", "completed_instances",
+                 "merges", "merge_bytes", "condition_payload_bytes", "path", "quiescent")
+DRAIN_COUNTERS = ("records", "value_bytes", "payload_bytes", "generic_tiles", "template_drain")
+
+
+def dump_outputs(out_dir, eng, st, ser, frames):
+    """What the last timed step handed its caller, as float64 / float32 .npy files (under 64 MB in all; the inputs
+    are counter-based, so two builds run with the same arguments are compared file by file):
+      step_counters.npy    zb_step's counters (STEP_COUNTERS order; no timings)
+      drain_counters.npy   zb_serialize's counters (DRAIN_COUNTERS order)
+      stream_sums.npy      the whole drained byte stream, per 256 MiB chunk: offset, bytes, sum of the bytes, sum of
+                           the little-endian u32 words (high and low 32 bits)
+      header_sums.npy      every drained header: records, sum of value_length, sum of key mod 2^64 (high and low 32
+                           bits), sums of record_type, value_type, intent, rejection_type
+      header_sample.npy    the headers of a fixed, seeded sample of record runs: index in the batch, key (high and low
+                           32 bits), record_type, value_type, intent, rejection_type, value_length, value_offset
+      value_sample.npy     those records' value bytes, concatenated in that order (one float32 per byte)
+    With --frames the batch has no headers: frame_sample_offsets.npy / frame_sample.npy hold seeded byte ranges of the
+    frame stream instead of the last three."""
+    import numpy as np
+
+    from zeebe_amd.engine import HEADER_DTYPE
+
+    os.makedirs(out_dir, exist_ok=True)
+
+    def save(name, arr, dtype=np.float64):
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(arr, dtype=dtype))
+
+    def split(v):  # an unsigned 64-bit sum as two exactly representable halves
+        v = int(v) & 0xFFFFFFFFFFFFFFFF
+        return [v >> 32, v & 0xFFFFFFFF]
+
+    save("step_counters", [st[k] for k in STEP_COUNTERS])
+    if ser is None:  # (--no-drain: the step hands out nothing else)
+        return
+    save("drain_counters", [ser[k] for k in DRAIN_COUNTERS])
+    total, count = ser["value_bytes"], ser["records"]
+    buf = np.empty(min(DUMP_CHUNK, max(total, 1)), dtype=np.uint8)
+    sums = []
+    for off in range(0, total, DUMP_CHUNK):
+        m = min(DUMP_CHUNK, total - off)
+        eng.drain_copy(buf.ctypes.data, off, m)
+        words = buf[:m & ~3].view("<u4").sum(dtype=np.uint64)
+        sums.append([off, m, int(buf[:m].sum(dtype=np.uint64))] + split(words))
+    save("stream_sums", np.array(sums, dtype=np.float64).reshape(-1, 5))
+    rng = np.random.default_rng(DUMP_SEED)
+    if frames:
+        last = max(total - DUMP_FRAME_WINDOW, 0) // 8
+        starts = sorted({0, last} | set(rng.integers(0, last + 1, size=DUMP_WINDOWS).tolist()))
+        starts = [8 * s for s in starts][:DUMP_SAMPLE_BYTES // DUMP_FRAME_WINDOW]
+        parts = []
+        for s in starts:
+            m = min(DUMP_FRAME_WINDOW, total - s)
+            eng.drain_copy(buf.ctypes.data, s, m)
+            parts.append(buf[:m].astype(np.float32))
+        save("frame_sample_offsets", starts)
+        save("frame_sample", np.concatenate(parts) if parts else [], dtype=np.float32)
+        return
+    hdr = np.empty(max(count, 1), dtype=HEADER_DTYPE)
+    eng.drain_copy(None, 0, 0, headers_ptr=hdr.ctypes.data)
+    hdr = hdr[:count]
+    save("header_sums", [count, int(hdr["value_length"].sum(dtype=np.uint64))] +
+         split(hdr["key"].astype(np.uint64).sum(dtype=np.uint64)) +
+         [int(hdr[k].sum(dtype=np.uint64)) for k in ("record_type", "value_type", "intent", "rejection_type")])
+    last = max(count - DUMP_WINDOW, 0)
+    starts = sorted({0, last} | set(rng.integers(0, last + 1, size=DUMP_WINDOWS).tolist()))
+    rows, parts, kept = [], [], 0
+    for s in starts:
+        h = hdr[s:s + DUMP_WINDOW]
+        if not len(h):
+            break
+        off, ln = h["value_offset"].astype(np.int64), h["value_length"].astype(np.int64)
+        lo, hi = int(off.min()), int((off + ln).max())
+        if kept + int(ln.sum()) > DUMP_SAMPLE_BYTES:
+            break
+        assert hi <= total and hi - lo <= len(buf), (s, lo, hi, total)
+        if hi > lo:
+            eng.drain_copy(buf.ctypes.data, lo, hi - lo)
+        for o, m in zip((off - lo).tolist(), ln.tolist()):
+            parts.append(buf[o:o + m].astype(np.float32))
+        kept += int(ln.sum())
+        key = h["key"].astype(np.uint64)
+        rows.append(np.stack([np.arange(s, s + len(h)), key >> np.uint64(32), key & np.uint64(0xFFFFFFFF),
+                              h["record_type"], h["value_type"], h["intent"], h["rejection_type"], ln, off],
+                             axis=1).astype(np.float64))
+    save("header_sample", np.concatenate(rows) if rows else np.zeros((0, 9)))
+    save("value_sample", np.concatenate(parts) if parts else [], dtype=np.float32)
 
 
 # ------------------------------------------------------------------------------ CPU baseline
@@ -483,7 +598,7 @@ def main():
     if a.steady:
         return run_steady_line(a, rank, world, local_rank, dist, barrier, reduce)
     tot = run_workload(a.config, n, a, rank, world, local_rank, barrier, a.steps, a.warmup, drain=not a.no_drain,
-                       pcie=(rank == 0 and world == 1 and not a.no_drain))
+                       pcie=(a.full and rank == 0 and world == 1 and not a.no_drain), dump=a.dump_outputs)
     elapsed = tot["elapsed"]
     all_tr, all_comp = tot["transitions"], tot["completed"]
     if dist is not None:
