@@ -14,6 +14,7 @@ import os
 import msgpack
 import pytest
 
+from drain_check import drain
 from zeebe_amd import bpmn, workloads
 
 pytestmark = pytest.mark.gpu
@@ -138,18 +139,15 @@ def test_size_pass_formula_matches_encoder():
 # ---- the template drain (zb_tdrain.hip): a uniform / class batch left without descriptors by zb_step, encoded
 # straight from its traces by zb_serialize of exactly its records; vs the descriptor path (ZB_CFG_NO_DEFER)
 def _template_drain(make, defer):
-    from zeebe_amd.engine import CFG_NO_DEFER, Engine, zb_record_header
+    from zeebe_amd.engine import CFG_NO_DEFER, Engine
 
     e = Engine(log_capacity=1 << 22, row_capacity=1 << 16, arena_bytes=64 << 20, flags=0 if defer else CFG_NO_DEFER)
     n = make(e)
     st = e.step()
     assert st["quiescent"] and st["path"] in (1, 2), st
     L = e.log_size()
-    ser = e.serialize(n, L - n)
-    vals = ctypes.create_string_buffer(max(ser["value_bytes"], 1))
-    hdrs = (zb_record_header * (L - n))()
-    e.drain_copy(ctypes.addressof(vals), 0, ser["value_bytes"], ctypes.addressof(hdrs))
-    out = dict(ser=ser, values=vals.raw[:ser["value_bytes"]], headers=bytes(hdrs))
+    ser, values, headers = drain(e, n)
+    out = dict(ser=ser, values=values, headers=headers)
     # then the descriptors (materialized on demand) and the records API
     out["desc"] = bytes(e.descriptors(0, L))
     out["records"] = e.records(n)

@@ -1188,7 +1188,7 @@ __device__ __forceinline__ void lds_words16(const uint8_t* p, uint32_t n, uint64
 
 struct Extract {  // per condition key: its first result, decoded
   uint32_t meta[CLS_QMAX];  // result count (saturating at 255) | token type << 8 | boolean << 16
-  uint32_t sp[CLS_QMAX];    // string / binary bytes: document offset | length << 16 (the LDS copy holds <= 96 bytes)
+  uint32_t sp[CLS_QMAX];    // string / binary bytes: document offset | length << 16 (documents below 64 KiB)
   uint64_t num[CLS_QMAX];   // integer, or the double's bits
   bool ok;
 };
@@ -1398,7 +1398,8 @@ __device__ __forceinline__ uint32_t outcome_key(const TrajParams& P, const uint8
   return key;
 }
 
-// classify: per-thread document slot [u32 len][document], an odd stride in words: 25 (documents <= 92 bytes) or, when
+// classify: per-thread document slot [u32 len][document], an odd stride in words: 25 (documents <= 92 bytes; longer
+// ones are read in place) or, when
 // every staged CREATE payload fits 44 bytes (P.max_create; C3's are <= 38), 13 -- the slots are what bounds the
 // occupancy (25: 5 workgroups per CU by LDS, 13: 8, at 64 VGPRs), and the kernel is latency-bound on its two dependent
 // loads per instance.
@@ -1434,12 +1435,18 @@ __global__ void __launch_bounds__(TWG) k_cls_classify(TrajParams P, InjectParams
     }
     const uint8_t* pp = P.arena + (uint64_t)ref * 8;
     const uint32_t len = *(const uint32_t*)pp;
-    // the VM inlined on the LDS copy (LDS loads per token); a document too large for the copy gets the
-    // error outcome at every split (its class, when it reaches one, sends the batch to the per-instance path)
+    // the VM inlined on the LDS copy (LDS loads per token); a document too large for the copy is read where it
+    // lies (the large-slot kernel only: global loads per token, as stage_doc's documents past its slot; lds_words16
+    // then reads up to 19 bytes past a string, inside ARENA_SLACK). One of 64 KiB or more (Extract.sp holds 16-bit
+    // offsets) gets the error outcome at every split: its class, when it reaches one, sends the batch to the
+    // per-instance path
     uint32_t key = 0;
     if (((len + 11) & ~7u) <= CL_STRIDE * 4) {  // (stage_copy writes whole 8-byte words)
       stage_copy(pp, len, s_doc + t * CL_STRIDE);
       const uint8_t* doc = (const uint8_t*)(s_doc + t * CL_STRIDE) + 4;
+      key = P.cls_nq ? outcome_key<true>(P, doc, len) : outcome_key<false>(P, doc, len);
+    } else if (CL_STRIDE == 25 && len < 65536) {
+      const uint8_t* doc = pp + 4;
       key = P.cls_nq ? outcome_key<true>(P, doc, len) : outcome_key<false>(P, doc, len);
     } else {
       for (int k = 0; k < P.nsplits; k++) key += (elem_ctl(P, P.split_elem[k]).cond_count() + 1) * P.split_stride[k];
