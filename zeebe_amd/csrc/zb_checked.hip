@@ -209,3 +209,18 @@ extern "C" unsigned long long zb_checked_violations(unsigned long long* launches
   if (launches) *launches = S.launches;
   return S.violations;
 }
+
+// test hook of the checked library: the engine allocations still live (every engine closed: what it left behind).
+// Their sites go to buf, newline-separated, as far as cap allows (always terminated when cap > 0).
+extern "C" size_t zb_checked_live(char* buf, size_t cap) {
+  zbg::State& S = zbg::st();
+  std::lock_guard<std::mutex> g(S.mu);
+  std::string all;
+  for (const auto& kv : S.live) all += kv.second.site + "\n";
+  if (buf && cap) {
+    const size_t n = all.size() < cap - 1 ? all.size() : cap - 1;
+    std::memcpy(buf, all.data(), n);
+    buf[n] = 0;
+  }
+  return S.live.size();
+}

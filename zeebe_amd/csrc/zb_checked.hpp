@@ -1,7 +1,8 @@
 // zb_checked.hpp — the guard-band build of the engine (libzbgpu_checked.so, `make checked`): a test instrument,
 // never the product library.
 //
-// Compiled with -DZB_CHECKED, every device allocation of the engine (hipMalloc) gets a guard band before and after
+// Compiled with -DZB_CHECKED, every device allocation of the engine (hipMalloc; the engine's own buffers, DevBuf in
+// zb_hostbuf.hpp, call checked_malloc with the member's name and the caller's line) gets a guard band before and after
 // the requested bytes, filled with a known pattern, and every kernel launch (hipLaunchKernelGGL) is followed by a
 // stream synchronisation and a device-side scan of every live guard band. A kernel (or a copy / memset queued
 // before it) that writes outside its buffer is reported with the allocation site, the side of the band and the

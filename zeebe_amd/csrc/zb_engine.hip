@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "zb_devlib.hpp"
+#include "zb_hostbuf.hpp"
 #include "zb_xmerge.hpp"
 #include "zb_kernels.hpp"
 #include "zb_model.hpp"
@@ -43,28 +44,6 @@ constexpr uint64_t TRAJ_BUDGET_BYTES = 256ull << 20;  // per-(generation, workgr
 constexpr int TRAJ_MAX_GENERATIONS = CLS_ROW;
 constexpr int TRAJ_WAVE_CAP = 8192;                   // k_traj_scan grid bound (one workgroup per generation)
 
-template <class T>
-struct DevVec {
-  T* p = nullptr;
-  size_t n = 0;
-  void free() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    n = 0;
-  }
-  hipError_t upload(const std::vector<T>& v, hipStream_t s) {
-    if (v.size() > n || !p) {
-      free();
-      size_t cap = v.empty() ? 1 : v.size();
-      hipError_t e = hipMalloc(&p, cap * sizeof(T));
-      if (e != hipSuccess) return e;
-      n = cap;
-    }
-    if (v.empty()) return hipSuccess;
-    return hipMemcpyAsync(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, s);
-  }
-};
-
 }  // namespace
 
 // a PUBLISH batch resident in p_in (zb_upload_publishes): byte offsets of its pieces
@@ -82,82 +61,83 @@ struct zb_engine {
   hipStream_t stream = nullptr;
   int32_t ncu = 256;            // compute units of the device
   int32_t wave_fused_grid = 0;  // k_wave: resident workgroups (0 = three-kernel pipeline; ZB_CFG_WAVE_SPLIT forces it)
-  uint64_t* lookback = nullptr; // k_wave hand-off granules (WaveParams.lookback)
+  DevBuf<uint64_t> lookback{"lookback"}; // k_wave hand-off granules (WaveParams.lookback)
   uint64_t lb_tiles = 0;
   uint64_t lb_seq = 0;          // k_wave launches (aggregate tags: 1 + lb_seq % 255)
   std::string err;
 
   ModelTables model;
-  DevVec<DevElem> d_elems;
-  DevVec<DevWorkflow> d_wfs;
-  DevVec<uint16_t> d_cond;
-  DevVec<uint32_t> d_code;
-  DevVec<uint32_t> d_cls_code;  // the program with the split conditions' path operands as extraction slots
-  DevVec<uint32_t> d_cls_atom;  // outcome table (k_cls_classify): the conditions' comparisons (their code words)
-  DevVec<uint8_t> d_cls_table;  //   and the class key of every combination of their outcomes
+  DevBuf<DevElem> d_elems{"d_elems"};
+  DevBuf<DevWorkflow> d_wfs{"d_wfs"};
+  DevBuf<uint16_t> d_cond{"d_cond"};
+  DevBuf<uint32_t> d_code{"d_code"};
+  DevBuf<uint32_t> d_cls_code{"d_cls_code"};  // the program with the split conditions' path operands as extraction slots
+  DevBuf<uint32_t> d_cls_atom{"d_cls_atom"};  // outcome table (k_cls_classify): the conditions' comparisons (their code words)
+  DevBuf<uint8_t> d_cls_table{"d_cls_table"};  //   and the class key of every combination of their outcomes
   int cls_natoms = 0;
-  DevVec<DevConst> d_consts;
-  DevVec<uint64_t> d_const_w;  // [consts][2] the bytes of string constants of at most 16 bytes (classify)
-  DevVec<DevQuery> d_queries;
-  DevVec<DevFilter> d_filters;
-  DevVec<uint8_t> d_pool;
-  DevVec<DevMapping> d_maps;
-  DevVec<DevSeg> d_segs;
+  DevBuf<DevConst> d_consts{"d_consts"};
+  DevBuf<uint64_t> d_const_w{"d_const_w"};  // [consts][2] the bytes of string constants of at most 16 bytes (classify)
+  DevBuf<DevQuery> d_queries{"d_queries"};
+  DevBuf<DevFilter> d_filters{"d_filters"};
+  DevBuf<uint8_t> d_pool{"d_pool"};
+  DevBuf<DevMapping> d_maps{"d_maps"};
+  DevBuf<DevSeg> d_segs{"d_segs"};
   bool has_io = false;          // some element has a zeebe:ioMapping (k_map runs, no trajectory path)
-  uint64_t* mapres = nullptr;   // k_map outcomes [wave_cap + 8]
-  MNode* map_ws = nullptr;      // k_map tree workspaces
+  DevBuf<uint64_t> mapres{"mapres"};   // k_map outcomes [wave_cap + 8]
+  DevBuf<MNode> map_ws{"map_ws"};      // k_map tree workspaces
   int ser_mode = 0;              // 0 = two passes (size, scan, write), 1 = single pass (look-back, ZB_CFG_SINGLE_PASS_DRAIN)
 
   // device state. The log arrays hold the window [win_base, win_base + log_capacity) of absolute positions;
   // log / links / srcd / vlen are biased pointers (index = absolute position) into the *_mem allocations, so
-  // every kernel indexes by position and the window moves by re-biasing (rebase_log)
+  // every kernel indexes by position and the window moves by re-biasing (rebase_log). Views, not owned:
   zb_rec* log = nullptr;
   uint64_t* links = nullptr;
   uint32_t* srcd = nullptr;     // per record: position - source position (0: none), for log frames
   uint32_t* vlen = nullptr;     // per record: serialized value length if the emitting kernel knew it
-  zb_rec* log_mem = nullptr;
-  uint64_t* links_mem = nullptr;
-  uint32_t* srcd_mem = nullptr;
-  uint32_t* vlen_mem = nullptr;
+  DevBuf<zb_rec> log_mem{"log_mem"};
+  DevBuf<uint64_t> links_mem{"links_mem"};
+  DevBuf<uint32_t> srcd_mem{"srcd_mem"};
+  DevBuf<uint32_t> vlen_mem{"vlen_mem"};
   int64_t win_base = 0;         // first position the device log holds (earlier ones were released / not restored)
   int64_t released = 0;         // zb_log_release: the caller appended everything below
-  DevVec<ValueConst> d_vconst;  // per element: constant parts of its WORKFLOW_INSTANCE / JOB values
-  DevVec<DevValSeg> d_vsegs;    // per element: its values' constant runs (fast drain passes)
-  DevVec<uint8_t> d_segpool;
+  DevBuf<ValueConst> d_vconst{"d_vconst"};  // per element: constant parts of its WORKFLOW_INSTANCE / JOB values
+  DevBuf<DevValSeg> d_vsegs{"d_vsegs"};    // per element: its values' constant runs (fast drain passes)
+  DevBuf<uint8_t> d_segpool{"d_segpool"};
   uint32_t segpool_len = 0;
   bool seg_ok = false;          // the runs fit the fast passes' LDS
-  uint32_t* vlen_bad = nullptr; // ZB_CFG_VLEN_CHECK: the size pass checks every known length (device flag)
-  uint8_t* row_mem = nullptr;   // element-instance rows: the three planes below, one allocation
-  RowMeta* rmeta = nullptr;     // [row_capacity]
-  RowKeys* rkeys = nullptr;     // [row_capacity]
-  RowLink* rlink = nullptr;     // [row_capacity]
-  uint8_t* arena = nullptr;
-  WaveHdr* hdr = nullptr;
-  uint32_t* derr = nullptr;
-  uint64_t* dstats = nullptr;
+  DevBuf<uint32_t> vlen_bad{"vlen_bad"}; // ZB_CFG_VLEN_CHECK: the size pass checks every known length (device flag)
+  DevBuf<uint8_t> row_mem{"row_mem"};   // element-instance rows: the three planes below, one allocation
+  RowMeta* rmeta = nullptr;     // view into row_mem: [row_capacity]
+  RowKeys* rkeys = nullptr;     // view into row_mem: [row_capacity]
+  RowLink* rlink = nullptr;     // view into row_mem: [row_capacity]
+  DevBuf<uint8_t> arena{"arena"};
+  DevBuf<WaveHdr> hdr{"hdr"};
+  DevBuf<uint32_t> derr{"derr"};
+  DevBuf<uint64_t> dstats{"dstats"};
   // wave staging (k_process -> k_scan -> k_emit), wave_cap records
   uint64_t wave_cap = 0;
-  uint64_t* cw = nullptr;
-  Slot* stage = nullptr;
-  ItemInfo* info = nullptr;
-  BlockAgg* block_agg = nullptr;
-  BlockOff* block_off = nullptr;
-  uint64_t* derr_info = nullptr;
-  MergeJob* merge_jobs = nullptr;
-  uint64_t* cond_jobs = nullptr;
-  uint32_t* job_counts = nullptr;  // [0..1] merge counts, [2..3] cond counts, [4..5] unused,
+  DevBuf<uint64_t> cw{"cw"};
+  DevBuf<Slot> stage{"stage"};
+  DevBuf<ItemInfo> info{"info"};
+  DevBuf<BlockAgg> block_agg{"block_agg"};
+  DevBuf<BlockOff> block_off{"block_off"};
+  DevBuf<uint64_t> derr_info{"derr_info"};
+  DevBuf<MergeJob> merge_jobs{"merge_jobs"};
+  DevBuf<uint64_t> cond_jobs{"cond_jobs"};
+  DevBuf<uint32_t> job_counts{"job_counts"};  // [0..1] merge counts, [2..3] cond counts, [4..5] unused,
                                    // [6..7] merges left to the general merger, [8..] subscribe counts [2][SUB_STRIPES]
-  uint32_t* merge_slow = nullptr;  // [job_cap] indices of those merges
-  unsigned long long* phase = nullptr;  // (ZB_PHASES measurement build) k_wave phase sums
+  DevBuf<uint32_t> merge_slow{"merge_slow"};  // [job_cap] indices of those merges
+  DevBuf<unsigned long long> phase{"phase"};  // (ZB_PHASES measurement build) k_wave phase sums
   PubUpload pub_up{};                   // a PUBLISH batch uploaded by zb_upload_publishes, not processed yet
+  // views lent by the device-wide pool (XPool), not owned:
   uint8_t* xslab = nullptr;        // exact payload tree workspaces (zb_xmerge.hpp), with a model that merges / maps
   uint32_t* xlocks = nullptr;
   uint8_t* xlane = nullptr;        // per-thread exact-tree workspaces (XLANE_COUNT x XLANE_BYTES), with xslab
   bool xpool_held = false;         // xslab / xlocks / xlane are the device's shared set (xpool_acquire)
-  uint64_t* sub_jobs = nullptr;    // [job_cap] subscribe steps of a wave (models with message catch events)
+  DevBuf<uint64_t> sub_jobs{"sub_jobs"};    // [job_cap] subscribe steps of a wave (models with message catch events)
   uint64_t job_cap = 0;
-  WaveHdr* h_hdr_pinned = nullptr;  // pinned mirror for D2H polling
-  uint32_t* h_err_pinned = nullptr;
+  PinBuf<WaveHdr> h_hdr_pinned{"h_hdr_pinned"};  // pinned mirror for D2H polling
+  PinBuf<uint32_t> h_err_pinned{"h_err_pinned"};
 
   int64_t wave = 0;
   WaveHdr host_hdr{};
@@ -171,7 +151,7 @@ struct zb_engine {
   // staged input
   std::vector<zb_rec> staged;
   std::vector<uint32_t> staged_vlen;   // value length of each staged record (VLEN_UNKNOWN: measured at drain)
-  DevVec<uint32_t> d_staged_vlen;
+  DevBuf<uint32_t> d_staged_vlen{"d_staged_vlen"};
   std::vector<uint8_t> staged_arena;
   struct PendingRange {
     int64_t first, last;  // staged indices
@@ -181,8 +161,8 @@ struct zb_engine {
     uint16_t pid_len;
   };
   std::vector<PendingRange> pending_ranges;
-  DevVec<zb_rec> d_staged;
-  DevVec<uint8_t> d_staged_arena;
+  DevBuf<zb_rec> d_staged{"d_staged"};
+  DevBuf<uint8_t> d_staged_arena{"d_staged_arena"};
   bool staged_uploaded = false;
   // Staged CREATE documents are uploaded in place, into the top of the arena (k_inject references them, no copy):
   // the device allocators grow [STATIC, arena_next) up to arena_top, and [arena_top, arena_bytes) holds the
@@ -198,37 +178,36 @@ struct zb_engine {
   // request metadata: of staged records (staged index), then of injected ones (log position, sorted)
   using StagedReq = zbg::StagedReq;
   std::vector<StagedReq> staged_reqs;
-  DevVec<StagedReq> d_staged_reqs;  // (uploaded with the staged batch)
+  DevBuf<StagedReq> d_staged_reqs{"d_staged_reqs"};  // (uploaded with the staged batch)
   bool staged_reqs_uploaded = false;
   // request metadata of the injected commands, device-resident and sorted by position (k_req_append at each injection,
   // no host copy): entries [req_lo, req_n) are live; one run per injection (its positions and entries)
-  ReqMeta* d_req = nullptr;
-  uint64_t req_cap = 0, req_lo = 0, req_n = 0;
+  DevBuf<ReqMeta> d_req{"d_req"};
+  uint64_t req_lo = 0, req_n = 0;
   struct ReqRun { int64_t first, last; uint64_t lo, n; };
   std::vector<ReqRun> req_runs;
 
   // submitted command ranges (serialization of CREATE commands / rejections)
   std::vector<CmdRange> ranges;
   std::vector<uint8_t> cmd_pool;
-  DevVec<CmdRange> d_ranges;
-  DevVec<uint8_t> d_cmd_pool;
+  DevBuf<CmdRange> d_ranges{"d_ranges"};
+  DevBuf<uint8_t> d_cmd_pool{"d_cmd_pool"};
 
   // trajectory path buffers (zb_traj.hip), grown on demand
   bool traj_model_ok = true;     // false when merges can precede condition evaluation (see zb_traj.hip)
   uint64_t traj_entries = 0;     // capacity of agg / woff in (generation, workgroup) entries
-  uint64_t* t_agg = nullptr;
-  uint4* t_woff = nullptr;
-  uint32_t* t_wcount = nullptr;
+  DevBuf<uint64_t> t_agg{"t_agg"};
+  DevBuf<uint4> t_woff{"t_woff"};
+  DevBuf<uint32_t> t_wcount{"t_wcount"};
   uint64_t t_nwg_cap = 0;
-  uint4* t_wtot = nullptr;
-  TrajBase* t_wbase = nullptr;
-  TrajCtl* t_ctl = nullptr;
-  uint64_t* t_xq = nullptr;        // the template emit's exact-tree queue (TrajParams.xq), one entry per instance
-  uint64_t t_xq_cap = 0;
-  MergeGen* t_mgen = nullptr;     // [TRAJ_MAX_GENERATIONS] uniform batch merge slots
-  uint64_t* t_wstats = nullptr;   // [t_nwg_cap + CLS_MAX][6] emit statistics per workgroup
-  TrajCtl* h_ctl_pinned = nullptr;
-  uint64_t* h_stats_pinned = nullptr;  // [0..7] counters before a step, [8..15] after, [16] a class batch's ClsPlan.nc,
+  DevBuf<uint4> t_wtot{"t_wtot"};
+  DevBuf<TrajBase> t_wbase{"t_wbase"};
+  DevBuf<TrajCtl> t_ctl{"t_ctl"};
+  DevBuf<uint64_t> t_xq{"t_xq"};        // the template emit's exact-tree queue (TrajParams.xq), one entry per instance
+  DevBuf<MergeGen> t_mgen{"t_mgen"};     // [TRAJ_MAX_GENERATIONS] uniform batch merge slots
+  DevBuf<uint64_t> t_wstats{"t_wstats"};   // [t_nwg_cap + CLS_MAX][6] emit statistics per workgroup
+  PinBuf<TrajCtl> h_ctl_pinned{"h_ctl_pinned"};
+  PinBuf<uint64_t> h_stats_pinned{"h_stats_pinned"};  // [0..7] counters before a step, [8..15] after, [16] a class batch's ClsPlan.nc,
                                        // [17] sort_pairs' key spread, [18] the waves counter before a wave loop,
                                        // [19..20] the outbox counts (zb_outbox_count)
   // class batches (zb_traj.hip k_cls_*): the model's exclusive splits as outcome-key digits
@@ -239,67 +218,60 @@ struct zb_engine {
   uint32_t cls_key_off[CLS_QMAX] = {}, cls_key_len[CLS_QMAX] = {};
   uint64_t cls_key_w[CLS_QMAX][2] = {};
   uint32_t split_elem[CLS_MAX_SPLITS] = {}, split_stride[CLS_MAX_SPLITS] = {};
-  ClsPlan* c_plan = nullptr;
+  DevBuf<ClsPlan> c_plan{"c_plan"};
   uint64_t cls_cap = 0;           // instances the class buffers hold
-  uint8_t* c_ikey = nullptr;
-  uint32_t* c_clen = nullptr;
-  uint32_t* d_cref = nullptr;  // [cref_cap] the last injected batch's payload refs (k_inject), at log position cref_base
-  uint64_t cref_cap = 0;
+  DevBuf<uint8_t> c_ikey{"c_ikey"};
+  DevBuf<uint32_t> c_clen{"c_clen"};
+  DevBuf<uint32_t> d_cref{"d_cref"};  // the last injected batch's payload refs (k_inject), at log position cref_base
   int64_t cref_base = -1;
-  uint32_t *c_khist = nullptr, *c_krep = nullptr;  // [CLS_HB][256] each (one allocation with c_klen)
-  uint64_t* c_klen = nullptr;                       // [CLS_HB][256]
-  TmplRec* t_tmpl = nullptr;     // [CLS_MAX][CLS_ROW][TF] traced records (uniform / class batches)
-  uint32_t* t_cstat = nullptr;   // [CLS_MAX][TSTAT]
-  uint64_t* c_mask = nullptr;
-  uint32_t* c_cg = nullptr;     // [groups][CLS_MAX][2] CREATE payload bytes per wave and class (k_cls_masks)
-  uint32_t *c_woffw = nullptr, *c_wgcnt = nullptr, *c_wgoff = nullptr, *c_perm = nullptr;
-  uint32_t *c_segs = nullptr, *c_wcls = nullptr;
+  DevBuf<uint32_t> c_khist{"c_khist"};  // [CLS_HB][256] key counts, then the two views below (one allocation)
+  uint32_t* c_krep = nullptr;   // view into c_khist: [CLS_HB][256]
+  uint64_t* c_klen = nullptr;   // view into c_khist: [CLS_HB][256]
+  DevBuf<TmplRec> t_tmpl{"t_tmpl"};     // [CLS_MAX][CLS_ROW][TF] traced records (uniform / class batches)
+  DevBuf<uint32_t> t_cstat{"t_cstat"};   // [CLS_MAX][TSTAT]
+  DevBuf<uint64_t> c_mask{"c_mask"};
+  DevBuf<uint32_t> c_cg{"c_cg"};     // [groups][CLS_MAX][2] CREATE payload bytes per wave and class (k_cls_masks)
+  DevBuf<uint32_t> c_woffw{"c_woffw"}, c_wgcnt{"c_wgcnt"}, c_wgoff{"c_wgoff"}, c_perm{"c_perm"};
+  DevBuf<uint32_t> c_segs{"c_segs"}, c_wcls{"c_wcls"};
 
   // message correlation (zb_msg.hip): outboxes [0] open-subscription, [1] correlate
-  zb_exchange_rec* obox[2] = {nullptr, nullptr};
-  uint64_t* okeys[2] = {nullptr, nullptr};
-  uint8_t* ovar[2] = {nullptr, nullptr};  // their commands' variable bytes
-  uint32_t* on = nullptr;  // [4] device counters: commands of [0] / [1], byte-section granules of [0] / [1]
+  DevBuf<zb_exchange_rec> obox[2]{{"obox[0]"}, {"obox[1]"}};
+  DevBuf<uint64_t> okeys[2]{{"okeys[0]"}, {"okeys[1]"}};
+  DevBuf<uint8_t> ovar[2]{{"ovar[0]"}, {"ovar[1]"}};  // their commands' variable bytes
+  DevBuf<uint32_t> on{"on"};  // [4] device counters: commands of [0] / [1], byte-section granules of [0] / [1]
   int64_t ob_pos_base[2] = {0, 0};  // Outbox.pos_base of [0] / [1]: the processing frontier at its last take
   uint64_t ocap = 0, ovar_cap = 0;        // commands, granules
   int64_t clock_ms = 0;                   // zb_set_clock (ActorClock of the message stream processor)
   // message batches / delivered exchange batches
-  uint8_t* m_prior = nullptr;
-  uint8_t* p_in = nullptr;        // zb_submit_publishes: the caller's keys / payloads / offsets on the device
-  uint64_t p_in_cap = 0;
-  uint64_t* p_gran = nullptr;     // [n + 1] blob granules, [n + 1] their scan, error flags
-  uint64_t p_gran_cap = 0;
-  uint64_t m_prior_cap = 0;
-  uint64_t* m_cnt = nullptr;
-  uint64_t m_cnt_cap = 0;
-  void* m_tmp = nullptr;
-  uint64_t m_tmp_cap = 0;
-  uint8_t* in_buf = nullptr;
-  uint64_t in_buf_cap = 0;
-  DevVec<uint64_t> d_slices;
+  DevBuf<uint8_t> m_prior{"m_prior"};
+  DevBuf<uint8_t> p_in{"p_in"};        // zb_submit_publishes: the caller's keys / payloads / offsets on the device
+  DevBuf<uint64_t> p_gran{"p_gran"};     // [n + 1] blob granules, [n + 1] their scan, error flags
+  DevBuf<uint64_t> m_cnt{"m_cnt"};
+  DevBuf<uint8_t> m_tmp{"m_tmp"};
+  DevBuf<uint8_t> in_buf{"in_buf"};
+  DevBuf<uint64_t> d_slices{"d_slices"};
   // message stores (MessageSubscriptionDataStore / MessageDataStore), allocated on first use
-  SubEntry* subs = nullptr;
-  uint32_t *sub_head = nullptr, *sub_next = nullptr;
-  MsgEntry* msgs = nullptr;
-  uint32_t *msg_head = nullptr, *msg_next = nullptr;
+  DevBuf<SubEntry> subs{"subs"};
+  DevBuf<uint32_t> sub_head{"sub_head"}, sub_next{"sub_next"};
+  DevBuf<MsgEntry> msgs{"msgs"};
+  DevBuf<uint32_t> msg_head{"msg_head"}, msg_next{"msg_next"};
   uint64_t store_cap = 0, head_mask = 0, sub_count = 0, msg_count = 0;
   int64_t msg_key_next = 0;  // message KeyGenerator(0, 1) (MessageService.java:91)
   bool has_catch = false;
   // RCCL communicator over the partitions of the node (zb_comm_*)
   ncclComm_t comm = nullptr;
   bool comm_broken = false;       // an RCCL call failed: the communicator is not used again
-  uint64_t* d_xcounts = nullptr;  // [4 * 64]: (count, status) pairs sent to / received from every rank
+  DevBuf<uint64_t> d_xcounts{"d_xcounts"};  // [4 * 64]: (count, status) pairs sent to / received from every rank
   // persistent exchange buffers, bytes (grown geometrically, never freed per round)
-  uint8_t* xsend = nullptr;
-  uint8_t* xrecv = nullptr;
-  uint64_t xsend_cap = 0, xrecv_cap = 0;
+  DevBuf<uint8_t> xsend{"xsend"};
+  DevBuf<uint8_t> xrecv{"xrecv"};
   // outbox sort buffers, sized to the outbox capacity once
-  uint64_t* ob_keys = nullptr;
-  uint32_t *ob_idx_in = nullptr, *ob_idx_out = nullptr;
-  uint64_t* ob_first = nullptr;  // [65]
-  uint32_t *ob_sizes = nullptr, *ob_goff = nullptr;
-  uint64_t *ob_table = nullptr, *ob_base = nullptr;
-  void* ob_tmp = nullptr;  // (scan scratch)
+  DevBuf<uint64_t> ob_keys{"ob_keys"};
+  DevBuf<uint32_t> ob_idx_in{"ob_idx_in"}, ob_idx_out{"ob_idx_out"};
+  DevBuf<uint64_t> ob_first{"ob_first"};  // [65]
+  DevBuf<uint32_t> ob_sizes{"ob_sizes"}, ob_goff{"ob_goff"};
+  DevBuf<uint64_t> ob_table{"ob_table"}, ob_base{"ob_base"};
+  DevBuf<uint8_t> ob_tmp{"ob_tmp"};  // (scan scratch)
   size_t ob_tmp_bytes = 0;
   uint32_t ob_counts_read[2] = {0, 0};  // both outbox command counts at the last zb_outbox_count
   // the outbox counters (commands, granules) in h_stats_pinned[19..20] are current: copied in the round trip that
@@ -313,11 +285,10 @@ struct zb_engine {
   int traj_skip = 0;     // batches left that skip the trajectory attempt after a fallback (zb_step)     // non-empty waves of the last step's wave loop (its first batch, zb_step)
   int ob_plan_kind = 0;  // the outbox kind outbox_plan sorted and sized last (0: none)
   uint64_t ob_plan_n = 0, ob_plan_total = 0, ob_plan_base[64] = {};
-  uint8_t* ob_staging = nullptr;
-  uint64_t ob_staging_cap = 0;
+  DevBuf<uint8_t> ob_staging{"ob_staging"};
 
   // scope-wide row state (RowAux), first-live-child requests, wave epoch
-  RowAux* raux = nullptr;
+  DevBuf<RowAux> raux{"raux"};
   int64_t epoch = 1;
   bool has_parallel = false;
   bool term = false;               // a CANCEL was injected: terminations may run until quiescence
@@ -330,68 +301,63 @@ struct zb_engine {
   std::unordered_set<int64_t> tick_aik;
   std::unordered_set<int64_t> tick_jobs;   // job keys with commands in the staged tick (one group each)
   std::unordered_set<int64_t> tick_conflicts;  // workflow instances whose staged records race (serialised by chunks)
-  DevVec<int64_t> d_conf_keys;             // their open-addressing table (uploaded with the batch)
-  int64_t* conf_first = nullptr;           // [conf_cap] + conf_split
-  uint64_t conf_cap = 0, conf_mask = 0, staged_conf = 0;
+  DevBuf<int64_t> d_conf_keys{"d_conf_keys"};             // their open-addressing table (uploaded with the batch)
+  DevBuf<int64_t> conf_first{"conf_first"};           // [its capacity - 1] + conf_split
+  uint64_t conf_mask = 0, staged_conf = 0;
   bool conf_active = false;                // the injected tick has conflicting instances: k_conflict every wave
-  JobTable jobs{};                         // ZB_CFG_JOB_PROCESSOR: job states by job key (open addressing)
+  JobTable jobs{};                         // ZB_CFG_JOB_PROCESSOR: job states by job key (open addressing),
+  DevBuf<int64_t> jobs_keys{"jobs.keys"};  //   its pointers views of these three
+  DevBuf<uint8_t> jobs_state{"jobs.state"};
+  DevBuf<uint32_t> jobs_tombs{"jobs.tombs"};
   // compaction (zb_compact.hip): scratch grown on demand, lifetime totals
-  uint32_t *c_flag = nullptr, *c_new = nullptr;  // scan input / output (live rows, live messages)
-  uint64_t c_flag_cap = 0, c_new_cap = 0;
-  void* c_tmp = nullptr;
-  size_t c_tmp_cap = 0;
-  uint8_t* c_scratch = nullptr;                  // live rows / live arena granules / live messages
-  uint64_t c_scratch_cap = 0;
-  uint64_t* c_bits = nullptr;                    // arena granule bitmap
-  uint64_t c_bits_cap = 0;
-  uint32_t *c_pop = nullptr, *c_off = nullptr;   // per-word popcounts and their scan
-  uint64_t c_pop_cap = 0, c_off_cap = 0;
-  uint32_t* c_count = nullptr;                   // device counter (job rebuild)
+  DevBuf<uint32_t> c_flag{"c_flag"}, c_new{"c_new"};  // scan input / output (live rows, live messages)
+  DevBuf<uint8_t> c_tmp{"c_tmp", 16};
+  DevBuf<uint8_t> c_scratch{"c_scratch"};                  // live rows / live arena granules / live messages
+  DevBuf<uint64_t> c_bits{"c_bits"};                    // arena granule bitmap
+  DevBuf<uint32_t> c_pop{"c_pop"}, c_off{"c_off"};   // per-word popcounts and their scan
+  DevBuf<uint32_t> c_count{"c_count"};                   // device counter (job rebuild)
   uint64_t rows_total = 0, arena_total = 0, records_total = 0, compactions = 0;  // lifetime allocation totals
   uint64_t rows_mark = 0, arena_mark = 0;  // rows / arena bytes live after the last compaction (maintain)
   // inbox CORRELATE resolution by activity instance key (zb_inbox_submit)
-  int64_t *x_keys = nullptr, *x_pos = nullptr, *x_keys2 = nullptr, *x_pos2 = nullptr;
-  uint32_t* d_unresolved = nullptr;  // delivered CORRELATEs whose token named no live row of their key (running count)
+  DevBuf<int64_t> x_keys{"x_keys"}, x_pos{"x_pos"}, x_keys2{"x_keys2"}, x_pos2{"x_pos2"};
+  DevBuf<uint32_t> d_unresolved{"d_unresolved"};  // delivered CORRELATEs whose token named no live row of their key (running count)
   // a class batch's injection, left to the classification kernel (run_trajectory), or to zb_step if that never ran
   bool inject_deferred = false;
   InjectParams inject_ip{};
   bool traj_stats_fresh = false;  // the last trajectory run's read-back holds the counters (h_stats_pinned + 8)
   // the outbox's counting sort: per bucket (commands << 40 | variable granules), their exclusive scan
-  unsigned long long *cs_cnt = nullptr, *cs_off = nullptr;
-  void* cs_tmp = nullptr;
-  uint64_t cs_cap = 0, cs_tmp_cap = 0;
+  DevBuf<unsigned long long> cs_cnt{"cs_cnt"}, cs_off{"cs_off"};
+  DevBuf<uint8_t> cs_tmp{"cs_tmp"};
+  uint64_t cs_cap = 0;  // buckets cs_cnt / cs_off hold (cs_tmp: its own capacity)
   bool ob_plan_cs = false;  // the plan is a local batch from the counting sort (outbox_emit: k_local_pack)
   uint32_t unresolved_seen = 0;
   uint64_t x_cap = 0;
-  DevVec<int64_t> d_lookup_keys, d_lookup_pos;    // zb_submit lookups of the staged batch: key, staged index
+  DevBuf<int64_t> d_lookup_keys{"d_lookup_keys"}, d_lookup_pos{"d_lookup_pos"};    // zb_submit lookups of the staged batch: key, staged index
   uint64_t staged_nlook = 0;
   uint64_t staged_lookup_spread = 0;  // OR of key ^ first key over the staged lookups (upload_staged)
-  int64_t *look_keys = nullptr, *look_idx = nullptr;  // sorted on the device by zb_step
-  uint64_t look_cap = 0;
+  DevBuf<int64_t> look_keys{"look_keys"}, look_idx{"look_idx"};  // sorted on the device by zb_step
   // radix sorts of (key, value) pairs (sort_pairs): scratch and the spread of the keys
-  uint8_t* sort_tmp = nullptr;
-  uint64_t sort_tmp_cap = 0;
-  uint64_t* d_spread = nullptr;
+  DevBuf<uint8_t> sort_tmp{"sort_tmp"};
+  DevBuf<uint64_t> d_spread{"d_spread"};
   // drain buffers (zb_serialize), grown on demand and reused
-  uint64_t dr_cap = 0, dr_val_cap = 0, dr_tmp_cap = 0;
-  uint32_t* dr_len = nullptr;  // value lengths
-  uint64_t *dr_off = nullptr, *dr_tiles = nullptr, *dr_pay = nullptr, *dr_tsum = nullptr;  // tile offsets / states / ...
-  uint8_t* h_stage = nullptr;    // pinned staging of host-built uploads (zb_submit_publishes)
-  size_t h_stage_cap = 0;
-  uint32_t* dr_list = nullptr;   // tiles the first fast pass leaves to the wide one
-  uint32_t* dr_list2 = nullptr;  // tiles for k_ser_write (left by either fast pass)
+  uint64_t dr_cap = 0;  // records the per-record / per-tile drain buffers hold (dr_val, dr_tmp: their own)
+  DevBuf<uint32_t> dr_len{"dr_len"};  // value lengths
+  DevBuf<uint64_t> dr_off{"dr_off"}, dr_tiles{"dr_tiles"}, dr_pay{"dr_pay"}, dr_tsum{"dr_tsum"};  // tile offsets / states / ...
+  PinBuf<uint8_t> h_stage{"h_stage"};    // pinned staging of host-built uploads (zb_submit_publishes)
+  DevBuf<uint32_t> dr_list{"dr_list"};   // tiles the first fast pass leaves to the wide one
+  DevBuf<uint32_t> dr_list2{"dr_list2"};  // tiles for k_ser_write (left by either fast pass)
   uint32_t dr_wide_tiles = 0;    // tiles the last drain's wide fast pass encoded
   uint32_t dr_slow_tiles = 0;    // how many tiles the last drain ran through k_ser_write
   bool dr_split = false;         // the last drain ran k_ser_fast + k_ser_write (events 2-4, 5-3)
   int ser_fast = 1;              // 0 (ZB_CFG_GENERIC_DRAIN): every tile through k_ser_write
   bool wave_events = false;      // ZB_CFG_WAVE_EVENTS: timing events around every wave's kernels
   int tmpl_io = 0;               // ZB_CFG_INSTANCE_ORDER: class batches emitted in instance order (k_tmpl_io)
-  zb_record_header* dr_hdr = nullptr;
-  uint8_t* dr_val = nullptr;
+  DevBuf<zb_record_header> dr_hdr{"dr_hdr"};
+  DevBuf<uint8_t> dr_val{"dr_val"};
   bool dr_frames = false;       // the drain batch holds log frames (no headers)
-  void* dr_tmp = nullptr;
-  uint64_t* dr_total = nullptr;   // [0] value bytes, [1] payload bytes (device)
-  uint64_t* h_dr_total = nullptr; // pinned mirror
+  DevBuf<uint8_t> dr_tmp{"dr_tmp", 16};
+  DevBuf<uint64_t> dr_total{"dr_total"};   // [0] value bytes, [1] payload bytes (device)
+  PinBuf<uint64_t> h_dr_total{"h_dr_total"}; // pinned mirror
   int64_t dr_count = 0;           // records of the batch in the drain buffers
   uint64_t dr_bytes = 0;
   uint64_t dr_epoch = 0;          // look-back tags of the single-pass serializer
@@ -406,20 +372,18 @@ struct zb_engine {
   int64_t seg_key_end = 0;  // every key and position the deferred batch's records carry is below this
   bool seg_jobs = false;    // the deferred batch created job keys
   TrajParams seg_p{};
-  uint64_t* td_wbytes = nullptr;  // [wmax * nwave + 1] (u64: hipcub's scan accumulates in the input type)
-  uint64_t* td_woffs = nullptr;
+  DevBuf<uint64_t> td_wbytes{"td_wbytes"};  // [wmax * nwave + 1] (u64: hipcub's scan accumulates in the input type)
+  DevBuf<uint64_t> td_woffs{"td_woffs"};
   uint64_t td_cap = 0;
-  void* td_tmp = nullptr;
-  size_t td_tmp_cap = 0;
-  uint64_t* td_pay = nullptr;     // [nwg]
-  uint64_t td_pay_cap = 0;
-  uint32_t* td_flags = nullptr;   // [2]
+  DevBuf<uint8_t> td_tmp{"td_tmp", 16};
+  DevBuf<uint64_t> td_pay{"td_pay"};     // [nwg]
+  DevBuf<uint32_t> td_flags{"td_flags"};   // [2]
 
   // timing
   std::vector<hipEvent_t> ev;
   // pinned upload ring (upload_async)
-  uint8_t* h_up = nullptr;
-  uint64_t h_up_cap = 0, h_up_off = 0;
+  PinBuf<uint8_t> h_up{"h_up"};
+  uint64_t h_up_off = 0;
 };
 
 namespace {
@@ -430,8 +394,8 @@ namespace {
 // has run by then); a copy larger than the ring goes the pageable way.
 hipError_t upload_async(zb_engine* e, void* dst, const void* src, size_t n) {
   if (n == 0) return hipSuccess;
-  if (!e->h_up || n > e->h_up_cap) return hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, e->stream);
-  if (e->h_up_off + n > e->h_up_cap) {
+  if (!e->h_up || n > e->h_up.cap()) return hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, e->stream);
+  if (e->h_up_off + n > e->h_up.cap()) {
     const hipError_t r = hipStreamSynchronize(e->stream);
     if (r != hipSuccess) return r;
     e->h_up_off = 0;
@@ -442,15 +406,11 @@ hipError_t upload_async(zb_engine* e, void* dst, const void* src, size_t n) {
   return hipMemcpyAsync(dst, at, n, hipMemcpyHostToDevice, e->stream);
 }
 template <class T>
-hipError_t upload_vec(zb_engine* e, DevVec<T>& d, const std::vector<T>& v) {
-  if (v.size() > d.n || !d.p) {
-    d.free();
-    const size_t cap = v.empty() ? 1 : v.size();
-    const hipError_t r = hipMalloc(&d.p, cap * sizeof(T));
-    if (r != hipSuccess) return r;
-    d.n = cap;
-  }
-  return upload_async(e, d.p, v.data(), v.size() * sizeof(T));
+hipError_t upload_vec(zb_engine* e, DevBuf<T>& d, const std::vector<T>& v, const char* file = __builtin_FILE(),
+                      int line = __builtin_LINE()) {
+  const hipError_t r = d.reserve(e->stream, std::max<size_t>(v.size(), 1), {}, file, line);
+  if (r != hipSuccess) return r;
+  return upload_async(e, d, v.data(), v.size() * sizeof(T));
 }
 
 // stream-ordered read-back of a few device words into pinned host memory with one launch (k_status) instead of one
@@ -475,13 +435,20 @@ struct StatusReads {
 // engine whose model merges or maps, freed with the last. Lanes that cannot be allocated leave the engines on the big-slab
 // path (XTree with lanes == nullptr) instead of failing the deploy.
 struct XPool {
-  uint8_t* slab = nullptr;
-  uint32_t* locks = nullptr;
-  uint8_t* lane = nullptr;
+  DevBuf<uint8_t> slab{"xpool.slab"};
+  DevBuf<uint32_t> locks{"xpool.locks"};
+  DevBuf<uint8_t> lane{"xpool.lane"};
   int refs = 0;
+  void reset() {
+    slab.reset();
+    locks.reset();
+    lane.reset();
+  }
 };
 std::mutex g_xpool_mu;
-std::map<int, XPool> g_xpool;
+// (never destroyed: a process that exits with engines open must not free device memory from a static destructor,
+// after the HIP runtime's own teardown)
+std::map<int, XPool>& g_xpool = *new std::map<int, XPool>();
 
 int fail(zb_engine* e, int code, const std::string& msg);
 
@@ -490,18 +457,14 @@ int xpool_acquire(zb_engine* e) {
   std::lock_guard<std::mutex> g(g_xpool_mu);
   XPool& x = g_xpool[e->cfg.device];
   if (!x.refs) {
-    if (hipMalloc(&x.slab, (size_t)XSLAB_COUNT * XSLAB_BYTES) != hipSuccess ||
-        hipMalloc(&x.locks, XLOCK_COUNT * sizeof(uint32_t)) != hipSuccess ||
+    if (x.slab.reserve(e->stream, (size_t)XSLAB_COUNT * XSLAB_BYTES) != hipSuccess ||
+        x.locks.reserve(e->stream, XLOCK_COUNT) != hipSuccess ||
         hipMemset(x.locks, 0, XLOCK_COUNT * sizeof(uint32_t)) != hipSuccess) {
-      if (x.slab) (void)hipFree(x.slab);
-      if (x.locks) (void)hipFree(x.locks);
-      x = XPool{};
+      x.reset();
       return fail(e, ZB_ENOMEM, "exact payload tree slabs");
     }
-    if (hipMalloc(&x.lane, (size_t)XLANE_COUNT * XLANE_BYTES) != hipSuccess) {
-      (void)hipGetLastError();
-      x.lane = nullptr;  // (the slab path)
-    }
+    if (x.lane.reserve(e->stream, (size_t)XLANE_COUNT * XLANE_BYTES) != hipSuccess)
+      (void)hipGetLastError();  // (lane stays empty: the slab path)
   }
   x.refs++;
   e->xslab = x.slab;
@@ -517,10 +480,7 @@ void xpool_release(zb_engine* e) {
   XPool& x = g_xpool[e->cfg.device];
   if (--x.refs == 0) {
     (void)hipDeviceSynchronize();  // (another engine's stream may still run a merge on it: none left now)
-    if (x.slab) (void)hipFree(x.slab);
-    if (x.locks) (void)hipFree(x.locks);
-    if (x.lane) (void)hipFree(x.lane);
-    x = XPool{};
+    x.reset();
   }
   e->xslab = nullptr;
   e->xlocks = nullptr;
@@ -549,11 +509,11 @@ uint32_t add_blob(std::vector<uint8_t>& arena, const uint8_t* p, uint32_t n) {
 }
 
 int upload_model(zb_engine* e) {
-  HIPCHECK(e, e->d_elems.upload(e->model.elems, e->stream));
-  HIPCHECK(e, e->d_wfs.upload(e->model.workflows, e->stream));
-  HIPCHECK(e, e->d_cond.upload(e->model.cond_flows, e->stream));
-  HIPCHECK(e, e->d_code.upload(e->model.code, e->stream));
-  HIPCHECK(e, e->d_consts.upload(e->model.consts, e->stream));
+  HIPCHECK(e, upload_vec(e, e->d_elems, e->model.elems));
+  HIPCHECK(e, upload_vec(e, e->d_wfs, e->model.workflows));
+  HIPCHECK(e, upload_vec(e, e->d_cond, e->model.cond_flows));
+  HIPCHECK(e, upload_vec(e, e->d_code, e->model.code));
+  HIPCHECK(e, upload_vec(e, e->d_consts, e->model.consts));
   {  // string constants as two little-endian words (k_cls_classify compares strings of <= 16 bytes as words)
     std::vector<uint64_t> w(2 * std::max<size_t>(e->model.consts.size(), 1), 0);
     for (size_t i = 0; i < e->model.consts.size(); i++) {
@@ -562,12 +522,12 @@ int upload_model(zb_engine* e) {
       for (uint32_t b = 0; b < c.str_len; b++)
         w[2 * i + b / 8] |= (uint64_t)e->model.pool[c.str_off + b] << (8 * (b % 8));
     }
-    HIPCHECK(e, e->d_const_w.upload(w, e->stream));
+    HIPCHECK(e, upload_vec(e, e->d_const_w, w));
   }
-  HIPCHECK(e, e->d_queries.upload(e->model.queries, e->stream));
-  HIPCHECK(e, e->d_filters.upload(e->model.filters, e->stream));
-  HIPCHECK(e, e->d_pool.upload(e->model.pool, e->stream));
-  HIPCHECK(e, e->d_maps.upload(e->model.maps, e->stream));
+  HIPCHECK(e, upload_vec(e, e->d_queries, e->model.queries));
+  HIPCHECK(e, upload_vec(e, e->d_filters, e->model.filters));
+  HIPCHECK(e, upload_vec(e, e->d_pool, e->model.pool));
+  HIPCHECK(e, upload_vec(e, e->d_maps, e->model.maps));
   {  // constant parts of the values an element's records carry (zb_serialize.hip encode_value)
     std::vector<ValueConst> vc(e->model.elems.size());
     for (size_t i = 0; i < vc.size(); i++) {
@@ -579,7 +539,7 @@ int upload_model(zb_engine* e) {
                   26 + mp_int_len(wf.version) + 12 + mp_int_len(wf.key) + 20 + 11 + id + 20 + 14 +
                   (el.headers_off == NO_REF ? 1 : el.headers_len) + 8;
     }
-    HIPCHECK(e, e->d_vconst.upload(vc, e->stream));
+    HIPCHECK(e, upload_vec(e, e->d_vconst, vc));
     // the fast drain passes' constant runs (zb_fastenc.hpp); the table padded to whole 16-byte LDS copies
     std::vector<DevValSeg> tab;
     std::vector<uint8_t> segs;
@@ -588,10 +548,10 @@ int upload_model(zb_engine* e) {
     tab.resize((tab.size() + 3) & ~(size_t)3, DevValSeg{});
     e->seg_ok = e->seg_ok && tab.size() * sizeof(DevValSeg) + segs.size() <= SEG_LDS_MAX;
     e->segpool_len = (uint32_t)segs.size();
-    HIPCHECK(e, e->d_vsegs.upload(tab, e->stream));
-    HIPCHECK(e, e->d_segpool.upload(segs, e->stream));
+    HIPCHECK(e, upload_vec(e, e->d_vsegs, tab));
+    HIPCHECK(e, upload_vec(e, e->d_segpool, segs));
   }
-  HIPCHECK(e, e->d_segs.upload(e->model.segs, e->stream));
+  HIPCHECK(e, upload_vec(e, e->d_segs, e->model.segs));
   if (e->static_blobs.size() > STATIC_ARENA_BYTES) return fail(e, ZB_ENOMEM, "static payload region full");
   HIPCHECK(e, hipMemcpyAsync(e->arena, e->static_blobs.data(), e->static_blobs.size(), hipMemcpyHostToDevice,
                              e->stream));
@@ -624,17 +584,17 @@ WaveParams wave_params(zb_engine* e) {
   p.rkeys = e->rkeys;
   p.rlink = e->rlink;
   p.arena = e->arena;
-  p.elems = e->d_elems.p;
-  p.wfs = e->d_wfs.p;
-  p.cond_flows = e->d_cond.p;
-  p.code = e->d_code.p;
-  p.consts = e->d_consts.p;
-  p.queries = e->d_queries.p;
-  p.filters = e->d_filters.p;
-  p.pool = e->d_pool.p;
-  p.vconst = e->d_vconst.p;
-  p.maps = e->d_maps.p;
-  p.segs = e->d_segs.p;
+  p.elems = e->d_elems;
+  p.wfs = e->d_wfs;
+  p.cond_flows = e->d_cond;
+  p.code = e->d_code;
+  p.consts = e->d_consts;
+  p.queries = e->d_queries;
+  p.filters = e->d_filters;
+  p.pool = e->d_pool;
+  p.vconst = e->d_vconst;
+  p.maps = e->d_maps;
+  p.segs = e->d_segs;
   p.mapres = e->mapres;
   p.map_ws = e->map_ws;
   p.hdr = e->hdr;
@@ -677,9 +637,9 @@ WaveParams wave_params(zb_engine* e) {
   p.term = e->term ? 1 : 0;
   p.epoch = e->epoch;
   p.conflicts = e->conf_active ? 1 : 0;
-  p.conf_keys = e->d_conf_keys.p;
+  p.conf_keys = e->d_conf_keys;
   p.conf_first = e->conf_first;
-  p.conf_split = e->conf_first ? e->conf_first + e->conf_cap : nullptr;
+  p.conf_split = e->conf_first ? e->conf_first + (e->conf_first.cap() - 1) : nullptr;
   p.conf_mask = e->conf_mask;
   // about four 256-record tiles per workgroup for the generation last seen by the host, 256..1024 workgroups
   // (C2 wave-only, 1M records per wave: 1024 workgroups 32.5 ms/step, 2048 33.0, 512 34.3, one tile per
@@ -727,36 +687,31 @@ uint64_t cls_slot_bound(uint64_t n, uint64_t nwg) {
 
 int grow_class_buffers(zb_engine* e, uint64_t n, uint64_t nwg) {
   if (n <= e->cls_cap) return ZB_OK;
-  void* ps[] = {e->c_ikey, e->c_clen, e->c_khist, e->c_mask, e->c_woffw, e->c_wgcnt, e->c_wgoff, e->c_perm, e->c_segs,
-                e->c_wcls, e->c_cg};
-  for (void* q : ps)
-    if (q) (void)hipFree(q);
-  e->c_ikey = nullptr; e->c_clen = nullptr; e->c_khist = e->c_krep = nullptr; e->c_klen = nullptr; e->c_mask = nullptr;
-  e->c_woffw = e->c_wgcnt = e->c_wgoff = e->c_perm = e->c_segs = e->c_wcls = nullptr;
-  e->c_cg = nullptr;
-  e->cls_cap = 0;
+  e->cls_cap = 0;  // (set again once every buffer of the group is in place)
+  e->c_krep = nullptr;
+  e->c_klen = nullptr;
   const uint64_t groups = nwg * (TRAJ_WG / 64);
   // per-instance arrays hold cls_cap = nwg * TRAJ_WG entries: a later batch of up to that many instances reuses them
   const uint64_t cap = nwg * TRAJ_WG;
-  HIPCHECK(e, hipMalloc(&e->c_ikey, cap));
-  HIPCHECK(e, hipMalloc(&e->c_clen, cap * sizeof(uint32_t)));
-  HIPCHECK(e, hipMalloc(&e->c_khist, CLS_HB * 256 * (2 * sizeof(uint32_t) + sizeof(uint64_t))));
+  HIPCHECK(e, e->c_ikey.renew(e->stream, cap));
+  HIPCHECK(e, e->c_clen.renew(e->stream, cap));
+  HIPCHECK(e, e->c_khist.renew(e->stream, CLS_HB * 256 * 4));  // (+ c_krep, + c_klen of twice the element size)
   e->c_krep = e->c_khist + CLS_HB * 256;
   e->c_klen = (uint64_t*)(e->c_khist + 2 * CLS_HB * 256);
   HIPCHECK(e, hipMemsetAsync(e->c_khist, 0, CLS_HB * 256 * sizeof(uint32_t), e->stream));
   HIPCHECK(e, hipMemsetAsync(e->c_klen, 0, CLS_HB * 256 * sizeof(uint64_t), e->stream));
   HIPCHECK(e, hipMemsetAsync(e->c_krep, 0xff, CLS_HB * 256 * sizeof(uint32_t), e->stream));
-  HIPCHECK(e, hipMalloc(&e->c_mask, groups * CLS_MAX * sizeof(uint64_t)));
-  HIPCHECK(e, hipMalloc(&e->c_cg, groups * CLS_MAX * 2 * sizeof(uint32_t)));
-  HIPCHECK(e, hipMalloc(&e->c_woffw, groups * CLS_MAX * sizeof(uint32_t)));
-  HIPCHECK(e, hipMalloc(&e->c_wgcnt, nwg * CLS_MAX * sizeof(uint32_t)));
-  HIPCHECK(e, hipMalloc(&e->c_wgoff, nwg * CLS_MAX * sizeof(uint32_t)));
+  HIPCHECK(e, e->c_mask.renew(e->stream, groups * CLS_MAX));
+  HIPCHECK(e, e->c_cg.renew(e->stream, groups * CLS_MAX * 2));
+  HIPCHECK(e, e->c_woffw.renew(e->stream, groups * CLS_MAX));
+  HIPCHECK(e, e->c_wgcnt.renew(e->stream, nwg * CLS_MAX));
+  HIPCHECK(e, e->c_wgoff.renew(e->stream, nwg * CLS_MAX));
   const uint64_t nblk = (nwg + CLS_BLK_WG - 1) / CLS_BLK_WG;
   const uint64_t slots = cls_slot_bound(cap, nwg);  // (for any batch of up to cap instances)
-  HIPCHECK(e, hipMalloc(&e->c_perm, slots * sizeof(uint32_t)));
-  HIPCHECK(e, hipMalloc(&e->c_segs, nblk * CLS_MAX * sizeof(uint32_t)));
-  HIPCHECK(e, hipMalloc(&e->c_wcls, (slots / 64 + 1) * sizeof(uint32_t)));
-  if (!e->c_plan) HIPCHECK(e, hipMalloc(&e->c_plan, sizeof(ClsPlan)));
+  HIPCHECK(e, e->c_perm.renew(e->stream, slots));
+  HIPCHECK(e, e->c_segs.renew(e->stream, nblk * CLS_MAX));
+  HIPCHECK(e, e->c_wcls.renew(e->stream, slots / 64 + 1));
+  HIPCHECK(e, e->c_plan.reserve(e->stream, 1));
   e->cls_cap = nwg * TRAJ_WG;
   return ZB_OK;
 }
@@ -767,22 +722,17 @@ int run_trajectory(zb_engine* e, int64_t log_base, int64_t n, zb_step_stats& st,
   uint64_t wcap = std::min<uint64_t>(TRAJ_MAX_GENERATIONS, (TRAJ_BUDGET_BYTES / per_entry) / nwg);
   if (wcap < 8 || nwg > 0x7fffffffull) return 0;
   if (wcap * nwg > e->traj_entries) {
-    if (e->t_agg) (void)hipFree(e->t_agg);
-    if (e->t_woff) (void)hipFree(e->t_woff);
-    e->t_agg = nullptr; e->t_woff = nullptr; e->traj_entries = 0;
+    e->traj_entries = 0;
     const uint64_t ent = TRAJ_BUDGET_BYTES / per_entry;
-    HIPCHECK(e, hipMalloc(&e->t_agg, ent * sizeof(uint64_t)));
-    HIPCHECK(e, hipMalloc(&e->t_woff, ent * sizeof(uint4)));
+    HIPCHECK(e, e->t_agg.renew(e->stream, ent));
+    HIPCHECK(e, e->t_woff.renew(e->stream, ent));
     e->traj_entries = ent;
   }
   if (nwg > e->t_nwg_cap) {
-    if (e->t_wcount) (void)hipFree(e->t_wcount);
-    if (e->t_wstats) (void)hipFree(e->t_wstats);
-    e->t_wcount = nullptr;
-    e->t_wstats = nullptr;
-    HIPCHECK(e, hipMalloc(&e->t_wcount, (nwg + CLS_MAX) * sizeof(uint32_t)));
+    e->t_nwg_cap = 0;
+    HIPCHECK(e, e->t_wcount.renew(e->stream, nwg + CLS_MAX));
     // (class batches emit over up to nwg + nwg / 8 + 8 workgroups)
-    HIPCHECK(e, hipMalloc(&e->t_wstats, (2 * nwg + 64) * 6 * sizeof(uint64_t)));
+    HIPCHECK(e, e->t_wstats.renew(e->stream, (2 * nwg + 64) * 6));
     e->t_nwg_cap = nwg;
   }
   TrajCtl c{};
@@ -792,25 +742,25 @@ int run_trajectory(zb_engine* e, int64_t log_base, int64_t n, zb_step_stats& st,
   HIPCHECK(e, hipMemcpyAsync(e->t_ctl, e->h_ctl_pinned, sizeof(TrajCtl), hipMemcpyHostToDevice, e->stream));
   TrajParams p{};
   p.log = e->log;
-  p.vconst = e->d_vconst.p;
+  p.vconst = e->d_vconst;
   p.srcd = e->srcd;
   p.vlen = e->vlen;
   p.arena = e->arena;
   p.rmeta = e->rmeta;
   p.rkeys = e->rkeys;
   p.rlink = e->rlink;
-  p.elems = e->d_elems.p;
-  p.cond_flows = e->d_cond.p;
-  p.code = e->d_code.p;
-  p.cls_code = e->d_cls_code.p;
-  p.consts = e->d_consts.p;
-  p.queries = e->d_queries.p;
-  p.filters = e->d_filters.p;
-  p.pool = e->d_pool.p;
+  p.elems = e->d_elems;
+  p.cond_flows = e->d_cond;
+  p.code = e->d_code;
+  p.cls_code = e->d_cls_code;
+  p.consts = e->d_consts;
+  p.queries = e->d_queries;
+  p.filters = e->d_filters;
+  p.pool = e->d_pool;
   p.log_base = log_base;
   p.n = n;
   // (the batch k_inject just wrote: its CREATE payload refs as a compact array)
-  p.cref = (e->d_cref && e->cref_base == log_base && (uint64_t)n <= e->cref_cap) ? e->d_cref : nullptr;
+  p.cref = (e->d_cref && e->cref_base == log_base && (uint64_t)n <= e->d_cref.cap()) ? e->d_cref.get() : nullptr;
   p.wf_start = e->host_hdr.wf_next;
   p.job_start = e->host_hdr.job_next;
   p.nwg = (int32_t)nwg;
@@ -831,7 +781,7 @@ int run_trajectory(zb_engine* e, int64_t log_base, int64_t n, zb_step_stats& st,
     // (block, class) segment padded to whole waves, a multiple of 8 workgroups (XCD mapping)
     // (a batch the drain may take from its traces skips the class-uniform slot layout: if it is emitted after all,
     // now or when materialized, the emit runs in instance order)
-    const bool may_defer = e->tmpl_defer && e->seg_ok && e->d_vsegs.p && e->d_vconst.p;
+    const bool may_defer = e->tmpl_defer && e->seg_ok && e->d_vsegs && e->d_vconst;
     p.io = e->tmpl_io || may_defer;
     if (!p.io) p.nwg_e = (int32_t)(((cls_slot_bound((uint64_t)n, nwg) + TRAJ_WG - 1) / TRAJ_WG + 7) & ~7ull);
     p.nblk = (int32_t)((nwg + CLS_BLK_WG - 1) / CLS_BLK_WG);
@@ -841,8 +791,8 @@ int run_trajectory(zb_engine* e, int64_t log_base, int64_t n, zb_step_stats& st,
     p.nsplits = e->nsplits;
     p.cls_nq = e->cls_nq;
     p.cls_natoms = e->cls_natoms;
-    p.cls_atom_w = e->d_cls_atom.p;
-    p.cls_table = e->d_cls_table.p;
+    p.cls_atom_w = e->d_cls_atom;
+    p.cls_table = e->d_cls_table;
     for (int j = 0; j < CLS_QMAX; j++) {
       p.cls_q[j] = e->cls_q[j];
       p.cls_key_off[j] = e->cls_key_off[j];
@@ -850,7 +800,7 @@ int run_trajectory(zb_engine* e, int64_t log_base, int64_t n, zb_step_stats& st,
       p.cls_key_w[j][0] = e->cls_key_w[j][0];
       p.cls_key_w[j][1] = e->cls_key_w[j][1];
     }
-    p.const_w = e->d_const_w.p;
+    p.const_w = e->d_const_w;
     for (int k = 0; k < CLS_MAX_SPLITS; k++) {
       p.split_elem[k] = e->split_elem[k];
       p.split_stride[k] = e->split_stride[k];
@@ -888,18 +838,12 @@ int run_trajectory(zb_engine* e, int64_t log_base, int64_t n, zb_step_stats& st,
   p.xlocks = e->xlocks;
   p.xlane = e->xlane;
   if (e->has_merges && e->xslab) {  // (a model that merges: refused pairs go to k_tmpl_xtree)
-    if ((uint64_t)n > e->t_xq_cap) {
-      if (e->t_xq) (void)hipFree(e->t_xq);
-      e->t_xq = nullptr;
-      e->t_xq_cap = 0;
-      HIPCHECK(e, hipMalloc(&e->t_xq, (uint64_t)n * sizeof(uint64_t)));
-      e->t_xq_cap = (uint64_t)n;
-    }
+    HIPCHECK(e, e->t_xq.reserve(e->stream, (uint64_t)n));
     p.xq = e->t_xq;
   }
   p.row_cap = e->cfg.row_capacity;
   p.arena_cap = e->arena_top;  // (the allocators' ceiling: staged documents above it)
-  p.defer_ok = (e->tmpl_defer && e->seg_ok && e->d_vsegs.p && e->d_vconst.p && (p.cls || p.uni)) ? 1 : 0;
+  p.defer_ok = (e->tmpl_defer && e->seg_ok && e->d_vsegs && e->d_vconst && (p.cls || p.uni)) ? 1 : 0;
   hipEvent_t* ev = e->ev.data();
   HIPCHECK(e, hipEventRecord(ev[0], e->stream));
   if (p.cls) {
@@ -985,31 +929,31 @@ int ensure_outbox(zb_engine* e) {
   // byte sections: 192 bytes per command on average (name + correlation key or payload), at least 64 MiB
   e->ovar_cap = std::max<uint64_t>(e->ocap * 24, 8ull << 20);
   for (int k = 0; k < 2; k++) {
-    HIPCHECK(e, hipMalloc(&e->obox[k], e->ocap * sizeof(zb_exchange_rec)));
-    HIPCHECK(e, hipMalloc(&e->okeys[k], e->ocap * sizeof(uint64_t)));
-    HIPCHECK(e, hipMalloc(&e->ovar[k], e->ovar_cap * 8));
+    HIPCHECK(e, e->obox[k].reserve(e->stream, e->ocap));
+    HIPCHECK(e, e->okeys[k].reserve(e->stream, e->ocap));
+    HIPCHECK(e, e->ovar[k].reserve(e->stream, e->ovar_cap * 8));
   }
-  HIPCHECK(e, hipMalloc(&e->on, 4 * sizeof(uint32_t)));
+  HIPCHECK(e, e->on.reserve(e->stream, 4));  // (last of the group: ensure_outbox's own test)
   HIPCHECK(e, hipMemsetAsync(e->on, 0, 4 * sizeof(uint32_t), e->stream));
   e->ob_counts_valid = false;
-  if (!e->sub_jobs) HIPCHECK(e, hipMalloc(&e->sub_jobs, e->job_cap * sizeof(uint64_t)));
+  HIPCHECK(e, e->sub_jobs.reserve(e->stream, e->job_cap));
   return ZB_OK;
 }
 
 int ensure_stores(zb_engine* e) {
   int rc = ensure_outbox(e);
   if (rc != ZB_OK) return rc;
-  if (e->subs) return ZB_OK;
+  if (e->msg_head) return ZB_OK;  // (the last of the group)
   e->store_cap = std::max<uint64_t>(e->cfg.row_capacity, 1024);
   uint64_t heads = 1;
   while (heads < 2 * e->store_cap) heads <<= 1;
   e->head_mask = heads - 1;
-  HIPCHECK(e, hipMalloc(&e->subs, e->store_cap * sizeof(SubEntry)));
-  HIPCHECK(e, hipMalloc(&e->sub_next, e->store_cap * sizeof(uint32_t)));
-  HIPCHECK(e, hipMalloc(&e->sub_head, heads * sizeof(uint32_t)));
-  HIPCHECK(e, hipMalloc(&e->msgs, e->store_cap * sizeof(MsgEntry)));
-  HIPCHECK(e, hipMalloc(&e->msg_next, e->store_cap * sizeof(uint32_t)));
-  HIPCHECK(e, hipMalloc(&e->msg_head, heads * sizeof(uint32_t)));
+  HIPCHECK(e, e->subs.reserve(e->stream, e->store_cap));
+  HIPCHECK(e, e->sub_next.reserve(e->stream, e->store_cap));
+  HIPCHECK(e, e->sub_head.reserve(e->stream, heads));
+  HIPCHECK(e, e->msgs.reserve(e->stream, e->store_cap));
+  HIPCHECK(e, e->msg_next.reserve(e->stream, e->store_cap));
+  HIPCHECK(e, e->msg_head.reserve(e->stream, heads));
   HIPCHECK(e, hipMemsetAsync(e->sub_head, 0xff, heads * sizeof(uint32_t), e->stream));
   HIPCHECK(e, hipMemsetAsync(e->msg_head, 0xff, heads * sizeof(uint32_t), e->stream));
   return ZB_OK;
@@ -1051,16 +995,8 @@ int sort_pairs(zb_engine* e, const K* kin, K* kout, const V* vin, V* vout, uint6
   if (rocprim::radix_sort_pairs<OnesweepSort>(nullptr, need, kin, kout, vin, vout, (size_t)n, begin, end,
                                               e->stream) != hipSuccess)
     return fail(e, ZB_EDEVICE, std::string(what) + ": sort sizing");
-  if (need + 16 > e->sort_tmp_cap) {
-    HIPCHECK(e, hipStreamSynchronize(e->stream));
-    if (e->sort_tmp) (void)hipFree(e->sort_tmp);
-    e->sort_tmp = nullptr;
-    e->sort_tmp_cap = 0;
-    const uint64_t c = std::max<uint64_t>(need + need / 2 + 16, 1 << 20);
-    HIPCHECK(e, hipMalloc(&e->sort_tmp, c));
-    e->sort_tmp_cap = c;
-  }
-  size_t have = e->sort_tmp_cap;
+  HIPCHECK(e, e->sort_tmp.reserve(e->stream, need + 16, Growth{0, need / 2, 1 << 20}));
+  size_t have = e->sort_tmp.cap();
   if (rocprim::radix_sort_pairs<OnesweepSort>(e->sort_tmp, have, kin, kout, vin, vout, (size_t)n, begin, end,
                                               e->stream) != hipSuccess)
     return fail(e, ZB_EDEVICE, std::string(what) + ": sort");
@@ -1097,10 +1033,10 @@ T* biased(T* mem, int64_t base) {
   return (T*)((uintptr_t)mem - (uintptr_t)base * sizeof(T));
 }
 void rebias(zb_engine* e) {
-  e->log = biased(e->log_mem, e->win_base);
-  e->links = biased(e->links_mem, e->win_base);
-  e->srcd = biased(e->srcd_mem, e->win_base);
-  e->vlen = biased(e->vlen_mem, e->win_base);
+  e->log = biased(e->log_mem.get(), e->win_base);
+  e->links = biased(e->links_mem.get(), e->win_base);
+  e->srcd = biased(e->srcd_mem.get(), e->win_base);
+  e->vlen = biased(e->vlen_mem.get(), e->win_base);
 }
 
 // Records the caller released move out of the window: [released, end) go to the front of the arrays (the
@@ -1121,24 +1057,21 @@ int append_requests(zb_engine* e, int64_t log_base) {
   const uint64_t m = e->staged_reqs.size();
   if (!m) return ZB_OK;
   if (!e->staged_reqs_uploaded) {
-    HIPCHECK(e, e->d_staged_reqs.upload(e->staged_reqs, e->stream));
+    HIPCHECK(e, upload_vec(e, e->d_staged_reqs, e->staged_reqs));
     e->staged_reqs_uploaded = true;
   }
-  if (e->req_n + m > e->req_cap) {  // grow, keeping only the live entries
+  if (e->req_n + m > e->d_req.cap()) {  // grow, keeping only the live entries
     const uint64_t live = e->req_n - e->req_lo;
-    const uint64_t cap = std::max<uint64_t>(2 * (live + m), 1024);
-    ReqMeta* p = nullptr;
-    HIPCHECK(e, hipMalloc(&p, cap * sizeof(ReqMeta)));
+    DevBuf<ReqMeta> p{"d_req"};
+    HIPCHECK(e, p.reserve(e->stream, std::max<uint64_t>(2 * (live + m), 1024)));
     if (live) HIPCHECK(e, hipMemcpyAsync(p, e->d_req + e->req_lo, live * sizeof(ReqMeta), hipMemcpyDeviceToDevice, e->stream));
     HIPCHECK(e, hipStreamSynchronize(e->stream));
-    if (e->d_req) (void)hipFree(e->d_req);
-    e->d_req = p;
-    e->req_cap = cap;
+    e->d_req.swap(p);  // (the old table goes with p)
     for (auto& r : e->req_runs) r.lo -= e->req_lo;
     e->req_n = live;
     e->req_lo = 0;
   }
-  launch_req_append(e->d_staged_reqs.p, m, log_base, e->d_req + e->req_n, e->stream);
+  launch_req_append(e->d_staged_reqs, m, log_base, e->d_req + e->req_n, e->stream);
   e->req_runs.push_back(zb_engine::ReqRun{log_base + e->staged_reqs.front().idx, log_base + e->staged_reqs.back().idx,
                                           e->req_n, m});
   e->req_n += m;
@@ -1175,16 +1108,19 @@ int rebase_log(zb_engine* e) {
   return ZB_OK;
 }
 
+// growth policies of the buffers that are sized on demand: a quarter over, at least 1024 elements; half over, at
+// least 1 MiB (byte buffers); the scan scratches (their 16 spare bytes are the member's pad)
+constexpr Growth GROW_QUARTER{4, 0, 1024};
+constexpr Growth GROW_HALF{2, 0, 1 << 20};
+constexpr Growth GROW_HALF_U64{2, 0, (1 << 20) / sizeof(uint64_t)};  // (the same bytes for 8-byte elements)
+constexpr Growth GROW_SCAN{4, 0, 0};
+
+// reserve with the engine's error reporting (queued work may still use the old buffer: reserve synchronises)
 template <class T>
-int grow(zb_engine* e, T** p, uint64_t* cap, uint64_t n) {
-  if (n <= *cap && *p) return ZB_OK;
-  HIPCHECK(e, hipStreamSynchronize(e->stream));  // (queued work may still use the old buffer)
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  const uint64_t c = std::max<uint64_t>(n + n / 4, 1024);
-  HIPCHECK(e, hipMalloc(p, c * sizeof(T)));
-  *cap = c;
+int reserve(zb_engine* e, DevBuf<T>& b, uint64_t n, Growth g, const char* file = __builtin_FILE(),
+            int line = __builtin_LINE()) {
+  const hipError_t r = b.reserve(e->stream, n, g, file, line);
+  if (r != hipSuccess) return fail(e, ZB_EDEVICE, std::string(b.name()) + ": " + hipGetErrorString(r));
   return ZB_OK;
 }
 
@@ -1194,15 +1130,9 @@ int scan_u32(zb_engine* e, const uint32_t* in, uint32_t* out, uint64_t n, uint64
   size_t tmp = 0;
   if (hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, in, out, (int)(n + 1), e->stream) != hipSuccess)
     return fail(e, ZB_EDEVICE, "compaction scan sizing");
-  if (tmp > e->c_tmp_cap) {
-    HIPCHECK(e, hipStreamSynchronize(e->stream));
-    if (e->c_tmp) (void)hipFree(e->c_tmp);
-    e->c_tmp = nullptr;
-    e->c_tmp_cap = 0;
-    HIPCHECK(e, hipMalloc(&e->c_tmp, tmp + tmp / 4 + 16));
-    e->c_tmp_cap = tmp + tmp / 4;
-  }
-  tmp = e->c_tmp_cap;
+  const int rc = reserve(e, e->c_tmp, tmp, GROW_SCAN);
+  if (rc != ZB_OK) return rc;
+  tmp = e->c_tmp.cap();
   if (hipcub::DeviceScan::ExclusiveSum(e->c_tmp, tmp, in, out, (int)(n + 1), e->stream) != hipSuccess)
     return fail(e, ZB_EDEVICE, "compaction scan");
   uint32_t t = 0;
@@ -1219,14 +1149,7 @@ int scan_reserve(zb_engine* e, uint64_t n) {
   if (hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)(n + 1),
                                        e->stream) != hipSuccess)
     return fail(e, ZB_EDEVICE, "compaction scan sizing");
-  if (tmp <= e->c_tmp_cap && e->c_tmp) return ZB_OK;
-  HIPCHECK(e, hipStreamSynchronize(e->stream));
-  if (e->c_tmp) (void)hipFree(e->c_tmp);
-  e->c_tmp = nullptr;
-  e->c_tmp_cap = 0;
-  HIPCHECK(e, hipMalloc(&e->c_tmp, tmp + tmp / 4 + 16));
-  e->c_tmp_cap = tmp + tmp / 4;
-  return ZB_OK;
+  return reserve(e, e->c_tmp, tmp, GROW_SCAN);
 }
 
 // The compaction buffers that scale with the capacities' index space, sized once when the engine is created: rows
@@ -1238,11 +1161,11 @@ int scan_reserve(zb_engine* e, uint64_t n) {
 int reserve_compaction(zb_engine* e) {
   const uint64_t nflag = std::max<uint64_t>(e->cfg.row_capacity, 1024) + 1;  // (rows; the stores hold as many)
   const uint64_t words_cap = ((e->cfg.arena_bytes - STATIC_ARENA_BYTES) / 8 + 63) / 64 + 1;
-  int rc = grow(e, &e->c_flag, &e->c_flag_cap, nflag);
-  if (rc == ZB_OK) rc = grow(e, &e->c_new, &e->c_new_cap, nflag);
-  if (rc == ZB_OK) rc = grow(e, &e->c_bits, &e->c_bits_cap, words_cap);
-  if (rc == ZB_OK) rc = grow(e, &e->c_pop, &e->c_pop_cap, words_cap + 1);
-  if (rc == ZB_OK) rc = grow(e, &e->c_off, &e->c_off_cap, words_cap + 1);
+  int rc = reserve(e, e->c_flag, nflag, GROW_QUARTER);
+  if (rc == ZB_OK) rc = reserve(e, e->c_new, nflag, GROW_QUARTER);
+  if (rc == ZB_OK) rc = reserve(e, e->c_bits, words_cap, GROW_QUARTER);
+  if (rc == ZB_OK) rc = reserve(e, e->c_pop, words_cap + 1, GROW_QUARTER);
+  if (rc == ZB_OK) rc = reserve(e, e->c_off, words_cap + 1, GROW_QUARTER);
   if (rc == ZB_OK) rc = scan_reserve(e, std::max(nflag, words_cap + 1));
   return rc;
 }
@@ -1254,14 +1177,7 @@ int reserve_compaction(zb_engine* e) {
 int reserve_gather(zb_engine* e) {
   const uint64_t row_bytes = sizeof(RowMeta) + sizeof(RowKeys) + sizeof(RowAux);
   const uint64_t full = std::max<uint64_t>(e->cfg.row_capacity * row_bytes, e->cfg.arena_bytes - STATIC_ARENA_BYTES);
-  if (e->c_scratch && e->c_scratch_cap >= full) return ZB_OK;
-  HIPCHECK(e, hipStreamSynchronize(e->stream));
-  if (e->c_scratch) (void)hipFree(e->c_scratch);
-  e->c_scratch = nullptr;
-  e->c_scratch_cap = 0;
-  HIPCHECK(e, hipMalloc(&e->c_scratch, full));
-  e->c_scratch_cap = full;
-  return ZB_OK;
+  return reserve(e, e->c_scratch, full, Growth{});
 }
 
 CompactParams compact_params(zb_engine* e) {
@@ -1308,10 +1224,10 @@ int compact_state(zb_engine* e) {
     rc = scan_u32(e, e->c_flag, e->c_new, rows, &live);
     if (rc != ZB_OK) return rc;
     const uint64_t row_bytes = ROW_BYTES + sizeof(RowAux);
-    rc = grow(e, &e->c_scratch, &e->c_scratch_cap, std::max<uint64_t>(live, 1) * row_bytes);
+    rc = reserve(e, e->c_scratch, std::max<uint64_t>(live, 1) * row_bytes, GROW_QUARTER);
     if (rc != ZB_OK) return rc;
     c.row_new = e->c_new;
-    c.m2 = (RowMeta*)e->c_scratch;
+    c.m2 = (RowMeta*)e->c_scratch.get();
     c.k2 = (RowKeys*)(e->c_scratch + live * sizeof(RowMeta));
     c.a2 = (RowAux*)(e->c_scratch + live * (sizeof(RowMeta) + sizeof(RowKeys)));
     launch_row_gather(c, e->stream);
@@ -1334,9 +1250,9 @@ int compact_state(zb_engine* e) {
     rc = scan_u32(e, e->c_flag, e->c_new, e->msg_count, &live_msgs);
     if (rc != ZB_OK) return rc;
     if (live_msgs != e->msg_count) {
-      rc = grow(e, &e->c_scratch, &e->c_scratch_cap, std::max<uint64_t>(live_msgs, 1) * sizeof(MsgEntry));
+      rc = reserve(e, e->c_scratch, std::max<uint64_t>(live_msgs, 1) * sizeof(MsgEntry), GROW_QUARTER);
       if (rc != ZB_OK) return rc;
-      launch_msg_gather(c, (MsgEntry*)e->c_scratch, e->stream);
+      launch_msg_gather(c, (MsgEntry*)e->c_scratch.get(), e->stream);
       if (live_msgs)
         HIPCHECK(e, hipMemcpyAsync(e->msgs, e->c_scratch, live_msgs * sizeof(MsgEntry), hipMemcpyDeviceToDevice, e->stream));
       e->msg_count = live_msgs;
@@ -1358,9 +1274,9 @@ int compact_state(zb_engine* e) {
   const uint64_t words = (dyn / 8 + 63) / 64;
   uint64_t granules = 0;
   if (words) {
-    rc = grow(e, &e->c_bits, &e->c_bits_cap, words);
-    if (rc == ZB_OK) rc = grow(e, &e->c_pop, &e->c_pop_cap, words + 1);
-    if (rc == ZB_OK) rc = grow(e, &e->c_off, &e->c_off_cap, words + 1);
+    rc = reserve(e, e->c_bits, words, GROW_QUARTER);
+    if (rc == ZB_OK) rc = reserve(e, e->c_pop, words + 1, GROW_QUARTER);
+    if (rc == ZB_OK) rc = reserve(e, e->c_off, words + 1, GROW_QUARTER);
     if (rc != ZB_OK) return rc;
     HIPCHECK(e, hipMemsetAsync(e->c_bits, 0, words * sizeof(uint64_t), e->stream));
     c.bits = e->c_bits; c.word_pop = e->c_pop; c.word_off = e->c_off; c.words = words;
@@ -1371,7 +1287,7 @@ int compact_state(zb_engine* e) {
     ZB_CT();  // arena marking
   }
   const bool room = STATIC_ARENA_BYTES + granules * 8 + pb <= e->cfg.arena_bytes;
-  rc = grow(e, &e->c_scratch, &e->c_scratch_cap, std::max<uint64_t>(granules * 8 + (pend_moves && room ? pb : 0), 8));
+  rc = reserve(e, e->c_scratch, std::max<uint64_t>(granules * 8 + (pend_moves && room ? pb : 0), 8), GROW_QUARTER);
   if (rc != ZB_OK) return rc;
   if (pend_moves && room)  // (stashed before the live bytes are copied back over the region it may lie in)
     HIPCHECK(e, hipMemcpyAsync(e->c_scratch + granules * 8, e->arena + e->staged_base, pb, hipMemcpyDeviceToDevice,
@@ -1406,11 +1322,11 @@ int compact_state(zb_engine* e) {
     HIPCHECK(e, hipStreamSynchronize(e->stream));
     if (tombs) {
       const uint64_t slots = e->jobs.mask + 1;
-      rc = grow(e, &e->c_scratch, &e->c_scratch_cap, slots * (sizeof(int64_t) + 1));
+      rc = reserve(e, e->c_scratch, slots * (sizeof(int64_t) + 1), GROW_QUARTER);
       if (rc != ZB_OK) return rc;
-      if (!e->c_count) HIPCHECK(e, hipMalloc(&e->c_count, sizeof(uint32_t)));
+      HIPCHECK(e, e->c_count.reserve(e->stream, 1));
       HIPCHECK(e, hipMemsetAsync(e->c_count, 0, sizeof(uint32_t), e->stream));
-      int64_t* keys = (int64_t*)e->c_scratch;
+      int64_t* keys = (int64_t*)e->c_scratch.get();
       uint8_t* st = e->c_scratch + slots * sizeof(int64_t);
       launch_job_collect(e->jobs, keys, st, e->c_count, e->stream);
       uint32_t n = 0;
@@ -1541,66 +1457,68 @@ int zb_engine_create(const zb_config* cfg, zb_engine** out) {
   const uint64_t L = e->cfg.log_capacity;
   e->wave_cap = e->cfg.wave_records ? e->cfg.wave_records : std::min<uint64_t>(L, 1ull << 22);
   e->wave_cap = (e->wave_cap + WAVE_TILE - 1) / WAVE_TILE * WAVE_TILE;
-  if (hipMalloc(&e->log_mem, L * sizeof(zb_rec)) != hipSuccess) return cleanup(ZB_ENOMEM);
-  if (hipMalloc(&e->links_mem, L * sizeof(uint64_t)) != hipSuccess) return cleanup(ZB_ENOMEM);
-  if (hipMalloc(&e->srcd_mem, L * sizeof(uint32_t)) != hipSuccess) return cleanup(ZB_ENOMEM);
-  if (hipMalloc(&e->vlen_mem, L * sizeof(uint32_t)) != hipSuccess) return cleanup(ZB_ENOMEM);
+  if (e->log_mem.reserve(e->stream, L) != hipSuccess) return cleanup(ZB_ENOMEM);
+  if (e->links_mem.reserve(e->stream, L) != hipSuccess) return cleanup(ZB_ENOMEM);
+  if (e->srcd_mem.reserve(e->stream, L) != hipSuccess) return cleanup(ZB_ENOMEM);
+  if (e->vlen_mem.reserve(e->stream, L) != hipSuccess) return cleanup(ZB_ENOMEM);
   rebias(e);
-  if ((e->cfg.flags & ZB_CFG_VLEN_CHECK) && hipMalloc(&e->vlen_bad, sizeof(uint32_t)) != hipSuccess)
+  if ((e->cfg.flags & ZB_CFG_VLEN_CHECK) && e->vlen_bad.reserve(e->stream, 1) != hipSuccess)
     return cleanup(ZB_ENOMEM);
   // job states: open addressing at load <= 1/2 for row_capacity live jobs
   if (e->cfg.flags & ZB_CFG_JOB_PROCESSOR) {
     uint64_t slots = 1024;
     while (slots < 2 * e->cfg.row_capacity) slots <<= 1;
     e->jobs.mask = slots - 1;
-    if (hipMalloc(&e->jobs.keys, slots * sizeof(int64_t)) != hipSuccess ||
-        hipMalloc(&e->jobs.state, slots) != hipSuccess || hipMalloc(&e->jobs.tombs, sizeof(uint32_t)) != hipSuccess)
+    if (e->jobs_keys.reserve(e->stream, slots) != hipSuccess ||
+        e->jobs_state.reserve(e->stream, slots) != hipSuccess || e->jobs_tombs.reserve(e->stream, 1) != hipSuccess)
       return cleanup(ZB_ENOMEM);
+    e->jobs.keys = e->jobs_keys;
+    e->jobs.state = e->jobs_state;
+    e->jobs.tombs = e->jobs_tombs;
   }
-  if (hipMalloc(&e->row_mem, e->cfg.row_capacity * ROW_BYTES) != hipSuccess) return cleanup(ZB_ENOMEM);
-  e->rmeta = (RowMeta*)e->row_mem;
+  if (e->row_mem.reserve(e->stream, e->cfg.row_capacity * ROW_BYTES) != hipSuccess) return cleanup(ZB_ENOMEM);
+  e->rmeta = (RowMeta*)e->row_mem.get();
   e->rkeys = (RowKeys*)(e->row_mem + e->cfg.row_capacity * sizeof(RowMeta));
   e->rlink = (RowLink*)(e->row_mem + e->cfg.row_capacity * (sizeof(RowMeta) + sizeof(RowKeys)));
   // (+ ARENA_SLACK: the drain's encoders load a payload document's first words without a bounds check)
-  if (hipMalloc(&e->arena, e->cfg.arena_bytes + ARENA_SLACK) != hipSuccess) return cleanup(ZB_ENOMEM);
-  if (hipMalloc(&e->hdr, 2 * sizeof(WaveHdr)) != hipSuccess) return cleanup(ZB_ENOMEM);
-  if (hipMalloc(&e->cw, e->wave_cap * sizeof(uint64_t)) != hipSuccess) return cleanup(ZB_ENOMEM);
-  if (hipMalloc(&e->stage, e->wave_cap * 2 * sizeof(Slot)) != hipSuccess) return cleanup(ZB_ENOMEM);
-  if (hipMalloc(&e->info, e->wave_cap * sizeof(ItemInfo)) != hipSuccess) return cleanup(ZB_ENOMEM);
-  if (hipMalloc(&e->block_agg, WAVE_GRID_MAX * sizeof(BlockAgg)) != hipSuccess) return cleanup(ZB_ENOMEM);
-  if (hipMalloc(&e->block_off, WAVE_GRID_MAX * sizeof(BlockOff)) != hipSuccess) return cleanup(ZB_ENOMEM);
+  if (e->arena.reserve(e->stream, e->cfg.arena_bytes + ARENA_SLACK) != hipSuccess) return cleanup(ZB_ENOMEM);
+  if (e->hdr.reserve(e->stream, 2) != hipSuccess) return cleanup(ZB_ENOMEM);
+  if (e->cw.reserve(e->stream, e->wave_cap) != hipSuccess) return cleanup(ZB_ENOMEM);
+  if (e->stage.reserve(e->stream, e->wave_cap * 2) != hipSuccess) return cleanup(ZB_ENOMEM);
+  if (e->info.reserve(e->stream, e->wave_cap) != hipSuccess) return cleanup(ZB_ENOMEM);
+  if (e->block_agg.reserve(e->stream, WAVE_GRID_MAX) != hipSuccess) return cleanup(ZB_ENOMEM);
+  if (e->block_off.reserve(e->stream, WAVE_GRID_MAX) != hipSuccess) return cleanup(ZB_ENOMEM);
   {
     e->lb_tiles = e->wave_cap / WAVE_TILE + 1;
     // (+ 1: the two k_wave tile counters)
     const size_t lb = (2 * e->lb_tiles + 8 * (e->lb_tiles + 512) + 8 * (e->lb_tiles + 2) + 1) * sizeof(uint64_t);
-    if (hipMalloc(&e->lookback, lb) != hipSuccess) return cleanup(ZB_ENOMEM);
+    if (e->lookback.reserve(e->stream, lb / sizeof(uint64_t)) != hipSuccess) return cleanup(ZB_ENOMEM);
     if (hipMemset(e->lookback, 0, lb) != hipSuccess) return cleanup(ZB_EDEVICE);
   }
-  if (hipMalloc(&e->derr, sizeof(uint32_t)) != hipSuccess) return cleanup(ZB_ENOMEM);
-  if (hipMalloc(&e->dstats, STAT_WORDS * sizeof(uint64_t)) != hipSuccess) return cleanup(ZB_ENOMEM);
-  if (hipMalloc(&e->derr_info, sizeof(uint64_t)) != hipSuccess) return cleanup(ZB_ENOMEM);
+  if (e->derr.reserve(e->stream, 1) != hipSuccess) return cleanup(ZB_ENOMEM);
+  if (e->dstats.reserve(e->stream, STAT_WORDS) != hipSuccess) return cleanup(ZB_ENOMEM);
+  if (e->derr_info.reserve(e->stream, 1) != hipSuccess) return cleanup(ZB_ENOMEM);
   e->job_cap = std::min<uint64_t>(L, 1ull << 26);
-  if (hipMalloc(&e->merge_jobs, 2 * e->job_cap * sizeof(MergeJob)) != hipSuccess) return cleanup(ZB_ENOMEM);
-  if (hipMalloc(&e->cond_jobs, 2 * e->job_cap * sizeof(uint64_t)) != hipSuccess) return cleanup(ZB_ENOMEM);
-  if (hipMalloc(&e->job_counts, JOB_COUNTS * sizeof(uint32_t)) != hipSuccess) return cleanup(ZB_ENOMEM);
-  if (hipMalloc(&e->merge_slow, e->job_cap * sizeof(uint32_t)) != hipSuccess) return cleanup(ZB_ENOMEM);
-  if (hipHostMalloc(&e->h_hdr_pinned, 2 * sizeof(WaveHdr)) != hipSuccess) return cleanup(ZB_ENOMEM);
-  if (hipHostMalloc(&e->h_err_pinned, 2 * sizeof(uint32_t)) != hipSuccess) return cleanup(ZB_ENOMEM);
-  if (hipHostMalloc(&e->h_ctl_pinned, sizeof(TrajCtl)) != hipSuccess) return cleanup(ZB_ENOMEM);
-  if (hipHostMalloc(&e->h_stats_pinned, 21 * sizeof(uint64_t)) != hipSuccess) return cleanup(ZB_ENOMEM);
-  if (hipHostMalloc(&e->h_up, 1 << 20) != hipSuccess) return cleanup(ZB_ENOMEM);
-  e->h_up_cap = 1 << 20;
-  if (hipMalloc(&e->d_spread, sizeof(uint64_t)) != hipSuccess) return cleanup(ZB_ENOMEM);
-  if (hipMalloc(&e->t_ctl, sizeof(TrajCtl)) != hipSuccess) return cleanup(ZB_ENOMEM);
-  if (hipMalloc(&e->t_wtot, TRAJ_WAVE_CAP * sizeof(uint4)) != hipSuccess) return cleanup(ZB_ENOMEM);
-  if (hipMalloc(&e->t_wbase, TRAJ_WAVE_CAP * sizeof(TrajBase)) != hipSuccess) return cleanup(ZB_ENOMEM);
-  if (hipMalloc(&e->t_mgen, CLS_MAX * CLS_ROW * sizeof(MergeGen)) != hipSuccess) return cleanup(ZB_ENOMEM);
-  if (hipMalloc(&e->t_tmpl, (size_t)CLS_MAX * CLS_ROW * TF * sizeof(TmplRec)) != hipSuccess) return cleanup(ZB_ENOMEM);
-  if (hipMalloc(&e->t_cstat, CLS_MAX * TSTAT * sizeof(uint32_t)) != hipSuccess) return cleanup(ZB_ENOMEM);
-  if (hipMalloc(&e->raux, e->cfg.row_capacity * sizeof(RowAux)) != hipSuccess) return cleanup(ZB_ENOMEM);
+  if (e->merge_jobs.reserve(e->stream, 2 * e->job_cap) != hipSuccess) return cleanup(ZB_ENOMEM);
+  if (e->cond_jobs.reserve(e->stream, 2 * e->job_cap) != hipSuccess) return cleanup(ZB_ENOMEM);
+  if (e->job_counts.reserve(e->stream, JOB_COUNTS) != hipSuccess) return cleanup(ZB_ENOMEM);
+  if (e->merge_slow.reserve(e->stream, e->job_cap) != hipSuccess) return cleanup(ZB_ENOMEM);
+  if (e->h_hdr_pinned.reserve(e->stream, 2) != hipSuccess) return cleanup(ZB_ENOMEM);
+  if (e->h_err_pinned.reserve(e->stream, 2) != hipSuccess) return cleanup(ZB_ENOMEM);
+  if (e->h_ctl_pinned.reserve(e->stream, 1) != hipSuccess) return cleanup(ZB_ENOMEM);
+  if (e->h_stats_pinned.reserve(e->stream, 21) != hipSuccess) return cleanup(ZB_ENOMEM);
+  if (e->h_up.reserve(e->stream, 1 << 20) != hipSuccess) return cleanup(ZB_ENOMEM);
+  if (e->d_spread.reserve(e->stream, 1) != hipSuccess) return cleanup(ZB_ENOMEM);
+  if (e->t_ctl.reserve(e->stream, 1) != hipSuccess) return cleanup(ZB_ENOMEM);
+  if (e->t_wtot.reserve(e->stream, TRAJ_WAVE_CAP) != hipSuccess) return cleanup(ZB_ENOMEM);
+  if (e->t_wbase.reserve(e->stream, TRAJ_WAVE_CAP) != hipSuccess) return cleanup(ZB_ENOMEM);
+  if (e->t_mgen.reserve(e->stream, CLS_MAX * CLS_ROW) != hipSuccess) return cleanup(ZB_ENOMEM);
+  if (e->t_tmpl.reserve(e->stream, (size_t)CLS_MAX * CLS_ROW * TF) != hipSuccess) return cleanup(ZB_ENOMEM);
+  if (e->t_cstat.reserve(e->stream, CLS_MAX * TSTAT) != hipSuccess) return cleanup(ZB_ENOMEM);
+  if (e->raux.reserve(e->stream, e->cfg.row_capacity) != hipSuccess) return cleanup(ZB_ENOMEM);
   if (hipMemset(e->raux, 0, e->cfg.row_capacity * sizeof(RowAux)) != hipSuccess) return cleanup(ZB_EDEVICE);
 #ifdef ZB_PHASES
-  if (hipMalloc(&e->phase, 16 * sizeof(unsigned long long)) != hipSuccess) return cleanup(ZB_ENOMEM);
+  if (e->phase.reserve(e->stream, 16) != hipSuccess) return cleanup(ZB_ENOMEM);
   if (hipMemset(e->phase, 0, 16 * sizeof(unsigned long long)) != hipSuccess) return cleanup(ZB_EDEVICE);
 #endif
   e->ev.resize(EV_PER_WAVE * WAVES_PER_SYNC_MAX);
@@ -1622,52 +1540,12 @@ void zb_engine_destroy(zb_engine* e) {
   if (e->stream) (void)hipStreamSynchronize(e->stream);
   for (auto& x : e->ev)
     if (x) (void)hipEventDestroy(x);
-  void* ps[] = {e->vlen_mem, e->vlen_bad, e->jobs.keys, e->jobs.state, e->jobs.tombs, e->c_flag, e->c_new, e->c_tmp,
-                e->c_scratch, e->c_bits, e->c_pop, e->c_off, e->c_count, e->x_keys, e->x_pos, e->x_keys2, e->x_pos2,
-                e->sort_tmp, e->d_spread, e->mapres, e->map_ws, e->log_mem, e->links_mem, e->srcd_mem, e->row_mem, e->arena, e->hdr, e->derr, e->dstats, e->derr_info,
-                e->merge_jobs, e->merge_slow, e->cond_jobs, e->job_counts, e->sub_jobs, e->cw, e->stage, e->info, e->block_agg, e->block_off, e->lookback,
-                e->t_agg, e->t_woff, e->t_wcount, e->t_wtot, e->t_wbase, e->t_ctl, e->t_mgen, e->t_wstats, e->t_xq,
-                e->c_plan, e->c_ikey, e->c_clen, e->d_cref, e->c_khist, e->c_mask, e->c_cg, e->c_woffw, e->c_wgcnt, e->c_wgoff, e->c_perm,
-                e->t_tmpl, e->t_cstat, e->c_segs, e->c_wcls, e->raux, e->look_keys, e->look_idx,
-                e->conf_first, e->phase};
-  for (void* p : ps)
-    if (p) (void)hipFree(p);
-  xpool_release(e);
-  if (e->comm) (void)ncclCommDestroy(e->comm);
-  void* ms[] = {e->obox[0], e->obox[1], e->okeys[0], e->okeys[1], e->ovar[0], e->ovar[1], e->on, e->subs, e->sub_head,
-                e->sub_next, e->msgs, e->msg_head, e->msg_next, e->d_xcounts, e->xsend, e->xrecv, e->ob_keys, e->ob_idx_in,
-                e->ob_idx_out, e->ob_first, e->ob_sizes, e->ob_goff, e->ob_table, e->ob_base, e->ob_tmp, e->ob_staging,
-                e->m_prior, e->m_cnt, e->m_tmp, e->in_buf, e->p_in, e->p_gran, e->d_unresolved, e->cs_cnt, e->cs_off,
-                e->cs_tmp};
-  for (void* p : ms)
-    if (p) (void)hipFree(p);
-  if (e->h_hdr_pinned) (void)hipHostFree(e->h_hdr_pinned);
-  if (e->h_err_pinned) (void)hipHostFree(e->h_err_pinned);
-  if (e->h_ctl_pinned) (void)hipHostFree(e->h_ctl_pinned);
-  if (e->h_stats_pinned) (void)hipHostFree(e->h_stats_pinned);
-  if (e->h_up) (void)hipHostFree(e->h_up);
-  e->d_elems.free(); e->d_wfs.free(); e->d_cond.free(); e->d_code.free(); e->d_cls_code.free(); e->d_cls_atom.free(); e->d_cls_table.free(); e->d_consts.free(); e->d_const_w.free();
-  e->d_queries.free(); e->d_filters.free(); e->d_pool.free(); e->d_staged.free(); e->d_staged_arena.free();
-  e->d_ranges.free(); e->d_cmd_pool.free(); e->d_lookup_keys.free(); e->d_lookup_pos.free();
-  e->d_maps.free();
-  e->d_segs.free();
-  e->d_vconst.free();
-  e->d_vsegs.free();
-  e->d_segpool.free();
-  e->d_staged_vlen.free();
-  e->d_staged_reqs.free();
-  if (e->d_req) (void)hipFree(e->d_req);
-  e->d_slices.free();
-  void* dr[] = {e->dr_len, e->dr_off, e->dr_hdr, e->dr_val, e->dr_tmp, e->dr_total, e->dr_tiles, e->dr_pay, e->dr_tsum,
-                e->dr_list, e->dr_list2};
-  for (void* p : dr)
-    if (p) (void)hipFree(p);
-  if (e->h_dr_total) (void)hipHostFree(e->h_dr_total);
-  if (e->h_stage) (void)hipHostFree(e->h_stage);
   for (auto& x : e->dr_ev)
     if (x) (void)hipEventDestroy(x);
+  xpool_release(e);
+  if (e->comm) (void)ncclCommDestroy(e->comm);
   if (e->stream) (void)hipStreamDestroy(e->stream);
-  delete e;
+  delete e;  // (every buffer frees itself)
 }
 
 #ifdef ZB_PHASES
@@ -1792,8 +1670,8 @@ int zb_deploy(zb_engine* e, int64_t workflow_key, int32_t version, const uint8_t
     if (el.kind == EK_TASK || el.step[WI_ELEMENT_ACTIVATED] == ST_CREATE_JOB) e->has_tasks = true;
   }
   if (e->has_io && !e->mapres) {
-    HIPCHECK(e, hipMalloc(&e->mapres, (e->wave_cap + 8) * sizeof(uint64_t)));
-    HIPCHECK(e, hipMalloc(&e->map_ws, (size_t)MAP_GRID * 256 * MAP_NODES * sizeof(MNode)));
+    HIPCHECK(e, e->map_ws.reserve(e->stream, (size_t)MAP_GRID * 256 * MAP_NODES));
+    HIPCHECK(e, e->mapres.reserve(e->stream, e->wave_cap + 8));  // (last: the test above)
   }
   if (e->has_io || e->has_merges) {  // payloads the structural merge / mapper refuse: the device's shared workspaces
     const int xrc = xpool_acquire(e);
@@ -1882,7 +1760,7 @@ int zb_deploy(zb_engine* e, int64_t workflow_key, int32_t version, const uint8_t
       }
     }
   }
-  HIPCHECK(e, e->d_cls_code.upload(cc, e->stream));
+  HIPCHECK(e, upload_vec(e, e->d_cls_code, cc));
   // The outcome table: with at most CLS_TABLE_ATOMS comparisons in the split conditions, the class key is a function
   // of their outcomes (false / true / error), which the conditions' programs give by this walk -- the control flow of
   // eval_condition_sweep: forward jumps on the last result, an error ends the condition (its split's digit: cc + 1)
@@ -1941,8 +1819,8 @@ int zb_deploy(zb_engine* e, int64_t workflow_key, int32_t version, const uint8_t
       if (ok) {
         std::vector<uint32_t> aw;  // (the code words themselves: no dependent load of the pc on the device)
         for (uint32_t pc : atoms) { aw.push_back(cc[2 * pc]); aw.push_back(cc[2 * pc + 1]); }
-        HIPCHECK(e, e->d_cls_atom.upload(aw, e->stream));
-        HIPCHECK(e, e->d_cls_table.upload(table, e->stream));
+        HIPCHECK(e, upload_vec(e, e->d_cls_atom, aw));
+        HIPCHECK(e, upload_vec(e, e->d_cls_table, table));
         e->cls_natoms = (int)atoms.size();
       }
     }
@@ -2026,12 +1904,12 @@ void begin_staging(zb_engine* e) {
 // the records that name an element instance (ElementInstanceIndex.getInstance), sorted by zb_step on the device
 int upload_staged(zb_engine* e) {
   if (e->staged_uploaded) return ZB_OK;
-  HIPCHECK(e, e->d_staged.upload(e->staged, e->stream));
+  HIPCHECK(e, upload_vec(e, e->d_staged, e->staged));
   if (!e->staged_reqs.empty() && !e->staged_reqs_uploaded) {
-    HIPCHECK(e, e->d_staged_reqs.upload(e->staged_reqs, e->stream));
+    HIPCHECK(e, upload_vec(e, e->d_staged_reqs, e->staged_reqs));
     e->staged_reqs_uploaded = true;
   }
-  HIPCHECK(e, e->d_staged_vlen.upload(e->staged_vlen, e->stream));
+  HIPCHECK(e, upload_vec(e, e->d_staged_vlen, e->staged_vlen));
   // the documents: in place at the top of the arena when they fit above the allocators' bytes (an earlier upload
   // of this same batch gives its room back first), else into a staging buffer that k_inject copies from
   if (e->staged_in_place) e->arena_top = e->staged_top;
@@ -2044,7 +1922,7 @@ int upload_staged(zb_engine* e) {
     e->arena_top = e->staged_base;
     e->staged_in_place = true;
   } else {
-    HIPCHECK(e, e->d_staged_arena.upload(e->staged_arena, e->stream));
+    HIPCHECK(e, upload_vec(e, e->d_staged_arena, e->staged_arena));
   }
   e->staged_nlook = 0;
   if (!e->staged_only_creates) {  // (CREATE-only batches name no element instance)
@@ -2058,8 +1936,8 @@ int upload_staged(zb_engine* e) {
       }
     e->staged_lookup_spread = spread;
     if (!lk.empty()) {
-      HIPCHECK(e, e->d_lookup_keys.upload(lk, e->stream));
-      HIPCHECK(e, e->d_lookup_pos.upload(li, e->stream));
+      HIPCHECK(e, upload_vec(e, e->d_lookup_keys, lk));
+      HIPCHECK(e, upload_vec(e, e->d_lookup_pos, li));
       HIPCHECK(e, hipStreamSynchronize(e->stream));  // (the host vectors die here)
     }
     e->staged_nlook = lk.size();
@@ -2074,14 +1952,8 @@ int upload_staged(zb_engine* e) {
       while (tab[h] != INT64_MIN) h = (h + 1) & (cap - 1);
       tab[h] = k;
     }
-    HIPCHECK(e, e->d_conf_keys.upload(tab, e->stream));
-    if (cap > e->conf_cap) {
-      HIPCHECK(e, hipStreamSynchronize(e->stream));
-      if (e->conf_first) (void)hipFree(e->conf_first);
-      e->conf_first = nullptr;
-      HIPCHECK(e, hipMalloc(&e->conf_first, (cap + 1) * sizeof(int64_t)));
-      e->conf_cap = cap;
-    }
+    HIPCHECK(e, upload_vec(e, e->d_conf_keys, tab));
+    HIPCHECK(e, e->conf_first.reserve(e->stream, cap + 1));  // [cap] + conf_split
     e->conf_mask = cap - 1;
     HIPCHECK(e, hipStreamSynchronize(e->stream));  // (the host table dies here)
   }
@@ -2640,22 +2512,16 @@ int zb_step(zb_engine* e, uint32_t max_waves, zb_step_stats* stats) {
     ip.links = e->links;
     ip.srcd = e->srcd;
     ip.vlen = e->vlen;
-    ip.staged_vlen = e->d_staged_vlen.p;
+    ip.staged_vlen = e->d_staged_vlen;
     ip.arena = e->arena;
-    ip.staged = e->d_staged.p;
-    ip.staged_arena = e->d_staged_arena.p;
+    ip.staged = e->d_staged;
+    ip.staged_arena = e->d_staged_arena;
     ip.n = n;
     ip.log_base = e->host_hdr.end;
     // documents in place: only the refs are rebased (the batch's documents are referenced where they lie)
     ip.arena_base = e->staged_in_place ? e->staged_base : (uint64_t)e->host_hdr.arena_next;
     ip.staged_bytes = e->staged_in_place ? 0 : e->staged_arena.size();
-    if ((uint64_t)n > e->cref_cap) {
-      if (e->d_cref) (void)hipFree(e->d_cref);
-      e->d_cref = nullptr;
-      e->cref_cap = 0;
-      HIPCHECK(e, hipMalloc(&e->d_cref, (uint64_t)n * sizeof(uint32_t)));
-      e->cref_cap = (uint64_t)n;
-    }
+    HIPCHECK(e, e->d_cref.reserve(e->stream, (uint64_t)n));
     ip.cref = e->d_cref;
     e->cref_base = ip.log_base;
     // a batch headed for the class path (run_trajectory: classify, then trace the classes) is injected by the
@@ -2673,20 +2539,12 @@ int zb_step(zb_engine* e, uint32_t max_waves, zb_step_stats* stats) {
     if (e->staged_nlook) {
       const uint64_t m = e->staged_nlook;
       if (m > (uint64_t)INT32_MAX) return fail(e, ZB_EUNSUPPORTED, "more than 2^31 staged lookups");
-      if (m > e->look_cap) {
-        HIPCHECK(e, hipStreamSynchronize(e->stream));
-        if (e->look_keys) (void)hipFree(e->look_keys);
-        if (e->look_idx) (void)hipFree(e->look_idx);
-        e->look_keys = e->look_idx = nullptr;
-        e->look_cap = 0;
-        const uint64_t c = std::max<uint64_t>(m + m / 4, 1024);
-        HIPCHECK(e, hipMalloc(&e->look_keys, c * sizeof(int64_t)));
-        HIPCHECK(e, hipMalloc(&e->look_idx, c * sizeof(int64_t)));
-        e->look_cap = c;
-      }
+      int rc = reserve(e, e->look_keys, m, GROW_QUARTER);
+      if (rc == ZB_OK) rc = reserve(e, e->look_idx, m, GROW_QUARTER);
+      if (rc != ZB_OK) return rc;
       e->h_stats_pinned[17] = e->staged_lookup_spread;  // (computed on the host by upload_staged)
-      int rc = sort_pairs(e, (const int64_t*)e->d_lookup_keys.p, e->look_keys, (const int64_t*)e->d_lookup_pos.p,
-                          e->look_idx, m, "lookup", true);
+      rc = sort_pairs(e, (const int64_t*)e->d_lookup_keys.get(), e->look_keys.get(), (const int64_t*)e->d_lookup_pos.get(),
+                          e->look_idx.get(), m, "lookup", true);
       if (rc != ZB_OK) return rc;
       ResolveParams rp{};
       rp.rmeta = e->rmeta; rp.rkeys = e->rkeys; rp.rows = (uint64_t)e->host_hdr.rows_next;
@@ -2953,27 +2811,18 @@ static int serialize_deferred(zb_engine* e, int64_t start, int64_t count, const 
   const uint64_t ent = (uint64_t)e->seg_wmax * nwave + 1;
   if (ent > (uint64_t)INT32_MAX) return ZB_EAGAIN;
   if (ent > e->td_cap) {
-    if (e->td_wbytes) (void)hipFree(e->td_wbytes);
-    if (e->td_woffs) (void)hipFree(e->td_woffs);
-    if (e->td_tmp) (void)hipFree(e->td_tmp);
-    e->td_wbytes = nullptr; e->td_woffs = nullptr; e->td_tmp = nullptr; e->td_cap = 0;
+    e->td_cap = 0;
     const uint64_t cap = ent + ent / 4 + 1024;
-    HIPCHECK(e, hipMalloc(&e->td_wbytes, cap * sizeof(uint64_t)));
-    HIPCHECK(e, hipMalloc(&e->td_woffs, cap * sizeof(uint64_t)));
+    HIPCHECK(e, e->td_wbytes.renew(e->stream, cap));
+    HIPCHECK(e, e->td_woffs.renew(e->stream, cap));
     size_t tmp = 0;
-    if (hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, e->td_wbytes, e->td_woffs, (int)cap, e->stream) != hipSuccess)
+    if (hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, e->td_wbytes.get(), e->td_woffs.get(), (int)cap, e->stream) != hipSuccess)
       return fail(e, ZB_EDEVICE, "template drain scan sizing");
-    HIPCHECK(e, hipMalloc(&e->td_tmp, tmp + 16));
-    e->td_tmp_cap = tmp;
+    HIPCHECK(e, e->td_tmp.renew(e->stream, tmp));
     e->td_cap = cap;
   }
-  if ((uint64_t)p.nwg > e->td_pay_cap) {
-    if (e->td_pay) (void)hipFree(e->td_pay);
-    e->td_pay = nullptr;
-    HIPCHECK(e, hipMalloc(&e->td_pay, (uint64_t)p.nwg * sizeof(uint64_t)));
-    e->td_pay_cap = (uint64_t)p.nwg;
-  }
-  if (!e->td_flags) HIPCHECK(e, hipMalloc(&e->td_flags, 4 * sizeof(uint32_t)));
+  HIPCHECK(e, e->td_pay.reserve(e->stream, (uint64_t)p.nwg));
+  HIPCHECK(e, e->td_flags.reserve(e->stream, 4));
   TDrainParams d{};
   d.t = p;
   d.headers = e->dr_hdr;
@@ -2985,8 +2834,8 @@ static int serialize_deferred(zb_engine* e, int64_t start, int64_t count, const 
   d.pay_part = e->td_pay;
   d.totals = e->dr_total;
   d.flags = e->td_flags;
-  d.vsegs = e->d_vsegs.p;
-  d.segpool = e->d_segpool.p;
+  d.vsegs = e->d_vsegs;
+  d.segpool = e->d_segpool;
   d.segpool_len = e->segpool_len;
   d.n_elems = (int32_t)e->model.elems.size();
   d.nc = e->seg_nc;
@@ -3014,7 +2863,7 @@ static int serialize_deferred(zb_engine* e, int64_t start, int64_t count, const 
   float ms_size = 0, ms_scan = 0, ms_write = 0;
   for (int attempt = 0; attempt < 2; attempt++) {
     d.out = e->dr_val;
-    d.out_cap = e->dr_val_cap;
+    d.out_cap = e->dr_val.cap();
     HIPCHECK(e, hipMemsetAsync(e->dr_total, 0, 4 * sizeof(uint64_t), e->stream));
     HIPCHECK(e, hipMemsetAsync(e->td_flags, 0, 4 * sizeof(uint32_t), e->stream));
     HIPCHECK(e, hipMemsetAsync(e->td_wbytes + (ent - 1), 0, sizeof(uint64_t), e->stream));
@@ -3029,8 +2878,8 @@ static int serialize_deferred(zb_engine* e, int64_t start, int64_t count, const 
     }
     launch_tdrain_size(d, wg0, e->stream);
     HIPCHECK(e, hipEventRecord(e->dr_ev[1], e->stream));
-    size_t tmp = e->td_tmp_cap;
-    if (hipcub::DeviceScan::ExclusiveSum(e->td_tmp, tmp, e->td_wbytes, e->td_woffs, (int)ent, e->stream) != hipSuccess)
+    size_t tmp = e->td_tmp.cap();
+    if (hipcub::DeviceScan::ExclusiveSum(e->td_tmp, tmp, e->td_wbytes.get(), e->td_woffs.get(), (int)ent, e->stream) != hipSuccess)
       return fail(e, ZB_EDEVICE, "template drain scan");
     HIPCHECK(e, hipMemcpyAsync(e->dr_total, e->td_woffs + (ent - 1), sizeof(uint64_t), hipMemcpyDeviceToDevice, e->stream));
     HIPCHECK(e, hipEventRecord(e->dr_ev[2], e->stream));
@@ -3044,12 +2893,7 @@ static int serialize_deferred(zb_engine* e, int64_t start, int64_t count, const 
     if (fl[1]) return ZB_EAGAIN;
     if (!fl[0]) break;
     if (attempt == 1) return fail(e, ZB_EDEVICE, "drain buffer overflow after growing it");
-    (void)hipFree(e->dr_val);
-    e->dr_val = nullptr;
-    e->dr_val_cap = 0;
-    const uint64_t cap = e->h_dr_total[0] + e->h_dr_total[0] / 4 + (64ull << 20);
-    HIPCHECK(e, hipMalloc(&e->dr_val, cap));
-    e->dr_val_cap = cap;
+    HIPCHECK(e, e->dr_val.renew(e->stream, e->h_dr_total[0] + e->h_dr_total[0] / 4 + (64ull << 20)));
   }
   HIPCHECK(e, hipEventElapsedTime(&ms_size, e->dr_ev[0], e->dr_ev[1]));
   HIPCHECK(e, hipEventElapsedTime(&ms_scan, e->dr_ev[1], e->dr_ev[2]));
@@ -3080,42 +2924,30 @@ static int serialize(zb_engine* e, int64_t start, int64_t count, const zb_frame_
   }
   if (!e->dr_ev[0])
     for (auto& x : e->dr_ev) HIPCHECK(e, hipEventCreate(&x));
-  if (!e->dr_total) {
-    HIPCHECK(e, hipMalloc(&e->dr_total, 4 * sizeof(uint64_t)));  // [0] bytes [1] payload bytes [2] ctr|overflow
-    HIPCHECK(e, hipHostMalloc(&e->h_dr_total, 4 * sizeof(uint64_t)));
-  }
+  HIPCHECK(e, e->dr_total.reserve(e->stream, 4));  // [0] bytes [1] payload bytes [2] ctr|overflow
+  HIPCHECK(e, e->h_dr_total.reserve(e->stream, 4));
   if ((uint64_t)count > e->dr_cap) {
-    void* ps[] = {e->dr_len, e->dr_off, e->dr_hdr, e->dr_tmp, e->dr_tiles, e->dr_pay, e->dr_tsum, e->dr_list, e->dr_list2};
-    for (void* q : ps)
-      if (q) (void)hipFree(q);
-    e->dr_off = e->dr_tiles = e->dr_pay = e->dr_tsum = nullptr; e->dr_len = e->dr_list = e->dr_list2 = nullptr;
-    e->dr_hdr = nullptr;
-    e->dr_tmp = nullptr;
-    e->dr_cap = e->dr_tmp_cap = 0;
+    e->dr_cap = 0;
     const uint64_t cap = (uint64_t)count + (uint64_t)count / 4 + 1024;
     if (cap + 1 > (uint64_t)INT32_MAX) return fail(e, ZB_EUNSUPPORTED, "more than 2^31 records in one drain");
-    HIPCHECK(e, hipMalloc(&e->dr_hdr, cap * sizeof(zb_record_header)));
-    HIPCHECK(e, hipMalloc(&e->dr_tiles, (cap / 256 + 2) * sizeof(uint64_t)));  // single pass: tile states
-    HIPCHECK(e, hipMalloc(&e->dr_pay, (cap / 256 + 2) * sizeof(uint64_t)));    // payload bytes per tile
+    HIPCHECK(e, e->dr_hdr.renew(e->stream, cap));
+    HIPCHECK(e, e->dr_tiles.renew(e->stream, cap / 256 + 2));  // single pass: tile states
+    HIPCHECK(e, e->dr_pay.renew(e->stream, cap / 256 + 2));    // payload bytes per tile
     HIPCHECK(e, hipMemset(e->dr_tiles, 0, (cap / 256 + 2) * sizeof(uint64_t)));
     // two passes: value lengths (u32 per record) and byte totals per 256-record tile -> tile offsets
-    HIPCHECK(e, hipMalloc(&e->dr_len, cap * sizeof(uint32_t)));
-    HIPCHECK(e, hipMalloc(&e->dr_tsum, (cap / 256 + 2) * sizeof(uint64_t)));
-    HIPCHECK(e, hipMalloc(&e->dr_off, (cap / 256 + 2) * sizeof(uint64_t)));
-    HIPCHECK(e, hipMalloc(&e->dr_list, (cap / 256 + 2) * sizeof(uint32_t)));
-    HIPCHECK(e, hipMalloc(&e->dr_list2, (cap / 256 + 2) * sizeof(uint32_t)));
+    HIPCHECK(e, e->dr_len.renew(e->stream, cap));
+    HIPCHECK(e, e->dr_tsum.renew(e->stream, cap / 256 + 2));
+    HIPCHECK(e, e->dr_off.renew(e->stream, cap / 256 + 2));
+    HIPCHECK(e, e->dr_list.renew(e->stream, cap / 256 + 2));
+    HIPCHECK(e, e->dr_list2.renew(e->stream, cap / 256 + 2));
     size_t tmp = 0;
-    if (hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, e->dr_tsum, e->dr_off, (int)(cap / 256 + 2), e->stream) != hipSuccess)
+    if (hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, e->dr_tsum.get(), e->dr_off.get(), (int)(cap / 256 + 2), e->stream) != hipSuccess)
       return fail(e, ZB_EDEVICE, "scan sizing");
-    HIPCHECK(e, hipMalloc(&e->dr_tmp, tmp + 16));
-    e->dr_tmp_cap = tmp;
+    HIPCHECK(e, e->dr_tmp.renew(e->stream, tmp));
     e->dr_cap = cap;
   }
-  if (e->dr_val_cap == 0) {  // first estimate; grown from the exact total if it overflows
-    const uint64_t cap = (uint64_t)count * 200 + (64ull << 20);
-    HIPCHECK(e, hipMalloc(&e->dr_val, cap));
-    e->dr_val_cap = cap;
-  }
+  if (!e->dr_val)  // first estimate; grown from the exact total if it overflows
+    HIPCHECK(e, e->dr_val.reserve(e->stream, (uint64_t)count * 200 + (64ull << 20)));
   if (e->seg_pending) {  // a deferred template batch: encoded from its traces, or materialized first
     if (start == e->seg_begin && count == e->seg_end - e->seg_begin) {
       const int rc = serialize_deferred(e, start, count, fc, st);
@@ -3153,18 +2985,18 @@ static int serialize(zb_engine* e, int64_t start, int64_t count, const zb_frame_
   sp.vlen_bad = e->vlen_bad;
   sp.arena = e->arena;
   sp.arena_bytes = e->cfg.arena_bytes;
-  sp.vconst = e->d_vconst.p;
-  sp.vsegs = e->d_vsegs.p;
-  sp.segpool = e->d_segpool.p;
+  sp.vconst = e->d_vconst;
+  sp.vsegs = e->d_vsegs;
+  sp.segpool = e->d_segpool;
   sp.segpool_len = e->segpool_len;
   sp.seg_lds = e->seg_ok ? 1 : 0;
-  sp.elems = e->d_elems.p;
-  sp.wfs = e->d_wfs.p;
-  sp.queries = e->d_queries.p;
-  sp.pool = e->d_pool.p;
-  sp.ranges = e->d_ranges.p;
+  sp.elems = e->d_elems;
+  sp.wfs = e->d_wfs;
+  sp.queries = e->d_queries;
+  sp.pool = e->d_pool;
+  sp.ranges = e->d_ranges;
   sp.nranges = (int32_t)e->ranges.size();
-  sp.cmd_pool = e->d_cmd_pool.p;
+  sp.cmd_pool = e->d_cmd_pool;
   sp.start = start;
   sp.count = count;
   sp.totals = e->dr_total;
@@ -3176,7 +3008,7 @@ static int serialize(zb_engine* e, int64_t start, int64_t count, const zb_frame_
   {
     const uint64_t need = ((sp.n_elems * sizeof(DevElem) + 15) & ~15ull) + ((sp.n_wfs * sizeof(DevWorkflow) + 15) & ~15ull) +
                           sp.pool_len;
-    sp.model_lds = (need <= 4096 && e->d_elems.p && e->d_wfs.p && e->d_pool.p) ? 1 : 0;
+    sp.model_lds = (need <= 4096 && e->d_elems && e->d_wfs && e->d_pool) ? 1 : 0;
   }
   sp.tile_ctr = (uint32_t*)(e->dr_total + 2);
   sp.overflow = (uint32_t*)(e->dr_total + 2) + 1;
@@ -3184,7 +3016,7 @@ static int serialize(zb_engine* e, int64_t start, int64_t count, const zb_frame_
   float ms_size = 0, ms_scan = 0, ms_write = 0;
   for (int attempt = 0; attempt < 2; attempt++) {
     sp.out = e->dr_val;
-    sp.out_cap = e->dr_val_cap;
+    sp.out_cap = e->dr_val.cap();
     HIPCHECK(e, hipMemsetAsync(e->dr_total, 0, 4 * sizeof(uint64_t), e->stream));
     e->dr_split = false;
     if (e->ser_mode == 1 && !fc) {  // one pass: decoupled look-back over 256-record tiles (values only)
@@ -3210,8 +3042,8 @@ static int serialize(zb_engine* e, int64_t start, int64_t count, const zb_frame_
       HIPCHECK(e, hipEventRecord(e->dr_ev[0], e->stream));
       launch_ser_size(sz, e->stream);
       HIPCHECK(e, hipEventRecord(e->dr_ev[1], e->stream));
-      size_t tmp = e->dr_tmp_cap;
-      if (hipcub::DeviceScan::ExclusiveSum(e->dr_tmp, tmp, e->dr_tsum, e->dr_off, (int)(tiles + 1), e->stream) != hipSuccess)
+      size_t tmp = e->dr_tmp.cap();
+      if (hipcub::DeviceScan::ExclusiveSum(e->dr_tmp, tmp, e->dr_tsum.get(), e->dr_off.get(), (int)(tiles + 1), e->stream) != hipSuccess)
         return fail(e, ZB_EDEVICE, "drain scan");
       HIPCHECK(e, hipMemcpyAsync(e->dr_total, e->dr_off + tiles, sizeof(uint64_t), hipMemcpyDeviceToDevice, e->stream));
       HIPCHECK(e, hipEventRecord(e->dr_ev[2], e->stream));
@@ -3272,12 +3104,7 @@ static int serialize(zb_engine* e, int64_t start, int64_t count, const zb_frame_
     const uint32_t overflow = ((const uint32_t*)(e->h_dr_total + 2))[1];
     if (!overflow) break;
     if (attempt == 1) return fail(e, ZB_EDEVICE, "drain buffer overflow after growing it");
-    (void)hipFree(e->dr_val);
-    e->dr_val = nullptr;
-    e->dr_val_cap = 0;
-    const uint64_t cap = e->h_dr_total[0] + e->h_dr_total[0] / 4 + (64ull << 20);
-    HIPCHECK(e, hipMalloc(&e->dr_val, cap));
-    e->dr_val_cap = cap;
+    HIPCHECK(e, e->dr_val.renew(e->stream, e->h_dr_total[0] + e->h_dr_total[0] / 4 + (64ull << 20)));
   }
   HIPCHECK(e, hipEventElapsedTime(&ms_size, e->dr_ev[0], e->dr_ev[1]));
   HIPCHECK(e, hipEventElapsedTime(&ms_scan, e->dr_ev[1], e->dr_ev[2]));
@@ -3338,14 +3165,7 @@ int zb_drain(zb_engine* e, int64_t start, int64_t count, zb_record_header* heade
 // pinned host staging for uploads built on the host (grown on demand; the stream is drained before reuse)
 static uint8_t* host_stage(zb_engine* e, size_t bytes) {
   if (hipStreamSynchronize(e->stream) != hipSuccess) return nullptr;
-  if (bytes > e->h_stage_cap) {
-    if (e->h_stage) (void)hipHostFree(e->h_stage);
-    e->h_stage = nullptr;
-    e->h_stage_cap = 0;
-    const size_t cap = bytes + bytes / 4 + (1 << 20);
-    if (hipHostMalloc(&e->h_stage, cap) != hipSuccess) return nullptr;
-    e->h_stage_cap = cap;
-  }
+  if (e->h_stage.reserve(e->stream, bytes, Growth{4, 1 << 20, 0}) != hipSuccess) return nullptr;
   return e->h_stage;
 }
 
@@ -3410,18 +3230,6 @@ int pull_header(zb_engine* e) {
   return ZB_OK;
 }
 
-int grow_dev(zb_engine* e, uint8_t** p, uint64_t* cap, uint64_t bytes) {
-  if (bytes <= *cap && *p) return ZB_OK;
-  HIPCHECK(e, hipStreamSynchronize(e->stream));
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  const uint64_t c = std::max<uint64_t>(bytes + bytes / 2, 1 << 20);
-  HIPCHECK(e, hipMalloc(p, c));
-  *cap = c;
-  return ZB_OK;
-}
-
 // exclusive scan of u64 in[0, n] into out (in[n] = 0); returns out[n]
 int scan_u64(zb_engine* e, uint64_t* in, uint64_t* out, uint64_t n, uint64_t* total) {
   if (n + 1 > (uint64_t)INT32_MAX) return fail(e, ZB_EUNSUPPORTED, "more than 2^31 commands in one batch");
@@ -3429,9 +3237,9 @@ int scan_u64(zb_engine* e, uint64_t* in, uint64_t* out, uint64_t n, uint64_t* to
   size_t tmp = 0;
   if (hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, in, out, (int)(n + 1), e->stream) != hipSuccess)
     return fail(e, ZB_EDEVICE, "scan sizing");
-  int rc = grow_dev(e, (uint8_t**)&e->m_tmp, &e->m_tmp_cap, tmp + 16);
+  int rc = reserve(e, e->m_tmp, tmp + 16, GROW_HALF);
   if (rc != ZB_OK) return rc;
-  tmp = e->m_tmp_cap;
+  tmp = e->m_tmp.cap();
   if (hipcub::DeviceScan::ExclusiveSum(e->m_tmp, tmp, in, out, (int)(n + 1), e->stream) != hipSuccess)
     return fail(e, ZB_EDEVICE, "scan");
   HIPCHECK(e, hipMemcpyAsync(total, out + n, sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream));
@@ -3483,7 +3291,7 @@ int process_messages(zb_engine* e, const MsgBatch& b) {
   }
   std::memcpy(stage + n * sizeof(zb_rec), b.blobs.data(), b.blobs.size());
   std::memcpy(stage + n * sizeof(zb_rec) + b.blobs.size(), b.prior.data(), n);
-  int rc = grow_dev(e, &e->m_prior, &e->m_prior_cap, n);
+  int rc = reserve(e, e->m_prior, n, GROW_HALF);
   if (rc != ZB_OK) return rc;
   HIPCHECK(e, hipMemcpyAsync(e->log + base, recs, n * sizeof(zb_rec), hipMemcpyHostToDevice, e->stream));
   HIPCHECK(e, hipMemcpyAsync(e->arena + arena0, stage + n * sizeof(zb_rec), b.blobs.size(), hipMemcpyHostToDevice, e->stream));
@@ -3507,7 +3315,7 @@ int process_uploaded_messages(zb_engine* e, uint64_t n, uint64_t blob_bytes,
                               const std::vector<std::pair<uint64_t, uint8_t>>& runs, int uniform_out) {
   const int64_t base = e->host_hdr.end;
   e->ob_counts_valid = false;  // (k_pub_emit writes correlations; finish_batch reads the counters back)
-  int rc = uniform_out ? ZB_OK : grow_dev(e, (uint8_t**)&e->m_cnt, &e->m_cnt_cap, 2 * (n + 1) * sizeof(uint64_t));
+  int rc = uniform_out ? ZB_OK : reserve(e, e->m_cnt, 2 * (n + 1), GROW_HALF_U64);
   if (rc != ZB_OK) return rc;
   if (!uniform_out) {
     HIPCHECK(e, hipMemsetAsync(e->links + base, 0xff, n * sizeof(uint64_t), e->stream));
@@ -3627,8 +3435,8 @@ int deliver(zb_engine* e, int kind, const uint8_t* buf, const std::vector<uint64
   MsgParams p = msg_params(e);
   p.in = buf;
   p.nslices = (int32_t)first.size();
-  p.slice_first = e->d_slices.p;
-  p.slice_off = e->d_slices.p + first.size();
+  p.slice_first = e->d_slices;
+  p.slice_off = e->d_slices + first.size();
   p.n = (int64_t)n;
   p.base = base;
   const int64_t arena_before = e->host_hdr.arena_next;
@@ -3644,22 +3452,17 @@ int deliver(zb_engine* e, int kind, const uint8_t* buf, const std::vector<uint64
     // names when that row still holds the key (live); the others -- a foreign or stale token -- are counted, and only
     // then are the keys sorted and the rows searched (k_resolve, below)
     if (!e->d_unresolved) {
-      HIPCHECK(e, hipMalloc(&e->d_unresolved, sizeof(uint32_t)));
+      HIPCHECK(e, e->d_unresolved.reserve(e->stream, 1));
       HIPCHECK(e, hipMemsetAsync(e->d_unresolved, 0, sizeof(uint32_t), e->stream));
       e->unresolved_seen = 0;
     }
     if (n > e->x_cap) {
-      HIPCHECK(e, hipStreamSynchronize(e->stream));
-      void* xs[] = {e->x_keys, e->x_pos, e->x_keys2, e->x_pos2};
-      for (void* q : xs)
-        if (q) (void)hipFree(q);
-      e->x_keys = e->x_pos = e->x_keys2 = e->x_pos2 = nullptr;
       e->x_cap = 0;
       const uint64_t c = std::max<uint64_t>(n + n / 2, 1024);
-      HIPCHECK(e, hipMalloc(&e->x_keys, c * 8));
-      HIPCHECK(e, hipMalloc(&e->x_pos, c * 8));
-      HIPCHECK(e, hipMalloc(&e->x_keys2, c * 8));
-      HIPCHECK(e, hipMalloc(&e->x_pos2, c * 8));
+      HIPCHECK(e, e->x_keys.renew(e->stream, c));
+      HIPCHECK(e, e->x_pos.renew(e->stream, c));
+      HIPCHECK(e, e->x_keys2.renew(e->stream, c));
+      HIPCHECK(e, e->x_pos2.renew(e->stream, c));
       e->x_cap = c;
     }
     if (n > (uint64_t)INT32_MAX) return fail(e, ZB_EUNSUPPORTED, "more than 2^31 delivered commands");
@@ -3692,7 +3495,7 @@ int deliver(zb_engine* e, int kind, const uint8_t* buf, const std::vector<uint64
   if (rc != ZB_OK) return rc;
   if (kind != ZB_XCHG_OPEN && *unres != e->unresolved_seen) {  // (a running count: no reset between deliveries)
     e->unresolved_seen = *unres;
-    rc = sort_pairs(e, e->x_keys, e->x_keys2, e->x_pos, e->x_pos2, n, "inbox");
+    rc = sort_pairs(e, e->x_keys.get(), e->x_keys2.get(), e->x_pos.get(), e->x_pos2.get(), n, "inbox");
     if (rc != ZB_OK) return rc;
     ResolveParams rp{};
     rp.rmeta = e->rmeta; rp.rkeys = e->rkeys; rp.rows = (uint64_t)e->host_hdr.rows_next;
@@ -3859,9 +3662,9 @@ int zb_upload_publishes(zb_engine* e, const char* name, int64_t ttl, size_t n, c
     body(0);
     for (auto& th : ths) th.join();
   }
-  rc = grow_dev(e, &e->p_in, &e->p_in_cap, total);
-  if (rc == ZB_OK) rc = grow_dev(e, (uint8_t**)&e->p_gran, &e->p_gran_cap, 2 * (n + 1) * sizeof(uint64_t) + 16);
-  if (rc == ZB_OK) rc = grow_dev(e, &e->m_prior, &e->m_prior_cap, n);
+  rc = reserve(e, e->p_in, total, GROW_HALF);
+  if (rc == ZB_OK) rc = reserve(e, e->p_gran, 2 * (n + 1) + 2, GROW_HALF_U64);
+  if (rc == ZB_OK) rc = reserve(e, e->m_prior, n, GROW_HALF);
   if (rc != ZB_OK) return rc;
   HIPCHECK(e, hipMemcpyAsync(e->p_in, stage, total, hipMemcpyHostToDevice, e->stream));
   // the batch checked and its blobs sized now (k_pub_sizes, scan): processing it needs no round trip for them
@@ -3925,8 +3728,8 @@ int zb_expire_messages(zb_engine* e, int64_t now_ms, uint64_t* n_deleted) {
   rc = maintain(e, false);
   if (rc != ZB_OK) return rc;
   const uint64_t m = e->msg_count;
-  rc = grow(e, &e->c_flag, &e->c_flag_cap, m + 1);
-  if (rc == ZB_OK) rc = grow(e, &e->c_new, &e->c_new_cap, m + 1);
+  rc = reserve(e, e->c_flag, m + 1, GROW_QUARTER);
+  if (rc == ZB_OK) rc = reserve(e, e->c_new, m + 1, GROW_QUARTER);
   if (rc != ZB_OK) return rc;
   MsgParams p = msg_params(e);
   p.now = now_ms;
@@ -3987,7 +3790,7 @@ int zb_inbox_submit(zb_engine* e, int kind, const uint8_t* batches, size_t bytes
   if (rc != ZB_OK) return rc;
   const uint8_t* dbuf = batches;
   if (!on_device) {
-    rc = grow_dev(e, &e->in_buf, &e->in_buf_cap, bytes);
+    rc = reserve(e, e->in_buf, bytes, GROW_HALF);
     if (rc != ZB_OK) return rc;
     HIPCHECK(e, hipMemcpyAsync(e->in_buf, batches, bytes, hipMemcpyHostToDevice, e->stream));
     dbuf = e->in_buf;
@@ -4057,17 +3860,18 @@ int outbox_plan(zb_engine* e, int kind, uint64_t* bytes_per_target, uint64_t* co
   if (rc != ZB_OK) return rc;
   *n_out = n;
   if (n == 0) return ZB_OK;
-  if (!e->ob_keys) {  // sort buffers, allocated once at the outbox capacity
+  if (!e->ob_tmp) {  // sort buffers, allocated once at the outbox capacity (the scan scratch last)
     const uint64_t c = e->ocap;
-    if (hipMalloc(&e->ob_keys, c * 8) != hipSuccess || hipMalloc(&e->ob_idx_in, c * 4) != hipSuccess ||
-        hipMalloc(&e->ob_idx_out, c * 4) != hipSuccess || hipMalloc(&e->ob_first, 65 * 8) != hipSuccess ||
-        hipMalloc(&e->ob_sizes, (c + 1) * 4) != hipSuccess || hipMalloc(&e->ob_goff, (c + 1) * 4) != hipSuccess ||
-        hipMalloc(&e->ob_table, 2 * 64 * 8) != hipSuccess || hipMalloc(&e->ob_base, 64 * 8) != hipSuccess)
+    hipStream_t s = e->stream;
+    if (e->ob_keys.reserve(s, c) != hipSuccess || e->ob_idx_in.reserve(s, c) != hipSuccess ||
+        e->ob_idx_out.reserve(s, c) != hipSuccess || e->ob_first.reserve(s, 65) != hipSuccess ||
+        e->ob_sizes.reserve(s, c + 1) != hipSuccess || e->ob_goff.reserve(s, c + 1) != hipSuccess ||
+        e->ob_table.reserve(s, 2 * 64) != hipSuccess || e->ob_base.reserve(s, 64) != hipSuccess)
       return fail(e, ZB_ENOMEM, "outbox sort buffers");
-    if (hipcub::DeviceScan::ExclusiveSum(nullptr, e->ob_tmp_bytes, e->ob_sizes, e->ob_goff, (int)(c + 1), e->stream) !=
+    if (hipcub::DeviceScan::ExclusiveSum(nullptr, e->ob_tmp_bytes, e->ob_sizes.get(), e->ob_goff.get(), (int)(c + 1), e->stream) !=
         hipSuccess)
       return fail(e, ZB_ENOMEM, "outbox scan scratch");
-    if (hipMalloc(&e->ob_tmp, e->ob_tmp_bytes + 16) != hipSuccess) return fail(e, ZB_ENOMEM, "outbox scan scratch");
+    if (e->ob_tmp.reserve(s, e->ob_tmp_bytes + 16) != hipSuccess) return fail(e, ZB_ENOMEM, "outbox scan scratch");
   }
   // the sort: by counting when the keys' spread is narrow and dense enough (a tick's commands: a position range a
   // few times the command count), else the radix sort over the spread's bits
@@ -4081,26 +3885,19 @@ int outbox_plan(zb_engine* e, int kind, uint64_t* bytes_per_target, uint64_t* co
   if (spread && cs_bits <= 24 && (1ull << cs_bits) <= 32 * n && n < (1ull << 24) && var_gran < (1ull << 40)) {
     const uint64_t nb = 1ull << cs_bits;
     size_t tmp = 0;
-    if (hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, e->cs_cnt, e->cs_off, (int)nb, e->stream) != hipSuccess)
+    if (hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, e->cs_cnt.get(), e->cs_off.get(), (int)nb, e->stream) != hipSuccess)
       return fail(e, ZB_EDEVICE, "outbox count scan sizing");
-    if (nb > e->cs_cap || tmp + 16 > e->cs_tmp_cap) {
-      HIPCHECK(e, hipStreamSynchronize(e->stream));
-      void* ps[] = {e->cs_cnt, e->cs_off, e->cs_tmp};
-      for (void* q : ps)
-        if (q) (void)hipFree(q);
-      e->cs_cnt = e->cs_off = nullptr;
-      e->cs_tmp = nullptr;
-      e->cs_cap = e->cs_tmp_cap = 0;
-      HIPCHECK(e, hipMalloc(&e->cs_cnt, nb * 8));
-      HIPCHECK(e, hipMalloc(&e->cs_off, nb * 8));
-      HIPCHECK(e, hipMalloc(&e->cs_tmp, tmp + 16));
+    if (nb > e->cs_cap || tmp + 16 > e->cs_tmp.cap()) {
+      e->cs_cap = 0;
+      HIPCHECK(e, e->cs_cnt.renew(e->stream, nb));
+      HIPCHECK(e, e->cs_off.renew(e->stream, nb));
+      HIPCHECK(e, e->cs_tmp.renew(e->stream, tmp + 16));
       e->cs_cap = nb;
-      e->cs_tmp_cap = tmp + 16;
     }
     HIPCHECK(e, hipMemsetAsync(e->cs_cnt, 0, nb * 8, e->stream));
     launch_cs_hist(ob, n, cs_begin, cs_bits, e->cs_cnt, e->stream);
-    size_t have = e->cs_tmp_cap;
-    if (hipcub::DeviceScan::ExclusiveSum(e->cs_tmp, have, e->cs_cnt, e->cs_off, (int)nb, e->stream) != hipSuccess)
+    size_t have = e->cs_tmp.cap();
+    if (hipcub::DeviceScan::ExclusiveSum(e->cs_tmp, have, e->cs_cnt.get(), e->cs_off.get(), (int)nb, e->stream) != hipSuccess)
       return fail(e, ZB_EDEVICE, "outbox count scan");
     if (local && P == 1) {  // the slots and variable places come out of the scatter (outbox_emit: k_local_pack)
       launch_cs_scatter(ob, n, cs_begin, cs_bits, e->cs_off, nullptr, e->ob_idx_out, e->ob_goff, e->stream);
@@ -4117,13 +3914,13 @@ int outbox_plan(zb_engine* e, int kind, uint64_t* bytes_per_target, uint64_t* co
     launch_cs_scatter(ob, n, cs_begin, cs_bits, e->cs_off, e->ob_keys, e->ob_idx_out, nullptr, e->stream);
   } else {
     launch_iota(e->ob_idx_in, n, e->stream);
-    rc = sort_pairs(e, (const uint64_t*)e->okeys[k], e->ob_keys, (const uint32_t*)e->ob_idx_in, e->ob_idx_out, n,
+    rc = sort_pairs(e, (const uint64_t*)e->okeys[k], e->ob_keys.get(), (const uint32_t*)e->ob_idx_in.get(), e->ob_idx_out.get(), n,
                     "outbox", true);
     if (rc != ZB_OK) return rc;
   }
   launch_outbox_sizes(ob, e->ob_idx_out, n, e->ob_sizes, e->stream);
   size_t tmp_bytes = e->ob_tmp_bytes;
-  if (hipcub::DeviceScan::ExclusiveSum(e->ob_tmp, tmp_bytes, e->ob_sizes, e->ob_goff, (int)(n + 1), e->stream) != hipSuccess)
+  if (hipcub::DeviceScan::ExclusiveSum(e->ob_tmp, tmp_bytes, e->ob_sizes.get(), e->ob_goff.get(), (int)(n + 1), e->stream) != hipSuccess)
     return fail(e, ZB_EDEVICE, "outbox scan");
   launch_outbox_bounds(e->ob_keys, n, e->ob_first, P, e->stream);
   if (local && P == 1) {  // (the command count and variable granules came with the count's round trip)
@@ -4194,11 +3991,11 @@ int zb_outbox_take(zb_engine* e, int kind, uint8_t* dst, size_t cap, int dst_on_
   if (!dst || cap < *total) return ZB_ENOMEM;
   uint8_t* out = dst;
   if (!dst_on_device) {
-    rc = grow_dev(e, &e->ob_staging, &e->ob_staging_cap, *total);
+    rc = reserve(e, e->ob_staging, *total, GROW_HALF);
     if (rc != ZB_OK) return rc;
     out = e->ob_staging;
   }
-  rc = outbox_emit(e, kind, out, dst_on_device ? cap : e->ob_staging_cap);
+  rc = outbox_emit(e, kind, out, dst_on_device ? cap : e->ob_staging.cap());
   if (rc != ZB_OK) return rc;
   if (!dst_on_device) HIPCHECK(e, hipMemcpyAsync(dst, e->ob_staging, *total, hipMemcpyDeviceToHost, e->stream));
   HIPCHECK(e, hipStreamSynchronize(e->stream));  // (the batches are complete on return)
@@ -4233,12 +4030,12 @@ int zb_comm_init(zb_engine* e, const uint8_t id[128], int nranks, int rank) {
   std::memcpy(&u, id, sizeof(u));
   NCCLCHECK(e, ncclCommInitRank(&e->comm, nranks, u, rank));
   e->comm_broken = false;
-  HIPCHECK(e, hipMalloc(&e->d_xcounts, 8 * 64 * sizeof(uint64_t)));
+  HIPCHECK(e, e->d_xcounts.reserve(e->stream, 8 * 64));
   int rc = ensure_outbox(e);
   if (rc != ZB_OK) return rc;
   // exchange buffers for the common case up front (grown later only if a round needs more)
-  rc = grow_dev(e, &e->xsend, &e->xsend_cap, 16ull << 20);
-  if (rc == ZB_OK) rc = grow_dev(e, &e->xrecv, &e->xrecv_cap, 16ull << 20);
+  rc = reserve(e, e->xsend, 16ull << 20, GROW_HALF);
+  if (rc == ZB_OK) rc = reserve(e, e->xrecv, 16ull << 20, GROW_HALF);
   return rc;
 }
 
@@ -4304,8 +4101,8 @@ int zb_comm_exchange(zb_engine* e, int kind, uint64_t* received) {
 #endif
   const bool self = P == 1 && !(e->cfg.flags & ZB_CFG_RCCL_SELF);
   if (local == ZB_OK) local = outbox_plan(e, kind, sb, sc, &n, &total, self);
-  if (local == ZB_OK && n) local = grow_dev(e, &e->xsend, &e->xsend_cap, total);
-  if (local == ZB_OK && n) local = outbox_emit(e, kind, e->xsend, e->xsend_cap);
+  if (local == ZB_OK && n) local = reserve(e, e->xsend, total, GROW_HALF);
+  if (local == ZB_OK && n) local = outbox_emit(e, kind, e->xsend, e->xsend.cap());
   if (P == 1 && !(e->cfg.flags & ZB_CFG_RCCL_SELF)) {  // no peer: the batch is this partition's own inbox
     if (local != ZB_OK || n == 0) return local;
     std::vector<uint64_t> rcounts{sc[0]}, roffs{0};
@@ -4343,7 +4140,7 @@ int zb_comm_exchange(zb_engine* e, int kind, uint64_t* received) {
     if (rtri[4 * q + 2] != 0 && peer_failed < 0) peer_failed = q;
   }
   // 2. the receive side may fail locally too: agree once more (max of the statuses) before any byte moves
-  if (peer_failed < 0 && local == ZB_OK && rbytes) local = grow_dev(e, &e->xrecv, &e->xrecv_cap, rbytes);
+  if (peer_failed < 0 && local == ZB_OK && rbytes) local = reserve(e, e->xrecv, rbytes, GROW_HALF);
   uint64_t st = (local != ZB_OK || peer_failed >= 0) ? 1 : 0;
   if (hipMemcpyAsync(e->d_xcounts + 448, &st, 8, hipMemcpyHostToDevice, e->stream) != hipSuccess)
     return comm_fail(e, "exchange status upload", ncclSystemError);
@@ -4481,24 +4278,18 @@ int zb_read_instances(zb_engine* e, uint8_t* buf, size_t cap, size_t* len, uint6
   *len = 0;
   if (count) *count = 0;
   if (rows == 0) return ZB_OK;
-  uint32_t* d_count = nullptr;
-  int64_t* d_keys = nullptr;
-  uint32_t* d_rows = nullptr;
-  zb_rec* d_descs = nullptr;
-  InstHead* d_heads = nullptr;
-  uint64_t *d_len = nullptr, *d_off = nullptr;
-  uint8_t* d_out = nullptr;
-  zb_record_header* d_hdrs = nullptr;
-  void* d_tmp = nullptr;
+  DevBuf<uint32_t> d_count{"d_count"}, d_rows{"d_rows"};  // (freed when the call returns)
+  DevBuf<int64_t> d_keys{"d_keys"};
+  DevBuf<zb_rec> d_descs{"d_descs"};
+  DevBuf<InstHead> d_heads{"d_heads"};
+  DevBuf<uint64_t> d_len{"d_len"}, d_off{"d_off"};
+  DevBuf<uint8_t> d_out{"d_out"};
+  DevBuf<zb_record_header> d_hdrs{"d_hdrs"};
+  hipStream_t s = e->stream;
   int rc = ZB_OK;
-  auto cleanup = [&]() {
-    void* ps[] = {d_count, d_keys, d_rows, d_descs, d_heads, d_len, d_off, d_out, d_hdrs, d_tmp};
-    for (void* q : ps)
-      if (q) (void)hipFree(q);
-  };
   do {
-    if (hipMalloc(&d_count, 4) != hipSuccess || hipMalloc(&d_keys, rows * 8) != hipSuccess ||
-        hipMalloc(&d_rows, rows * 4) != hipSuccess) { rc = fail(e, ZB_ENOMEM, "read_instances buffers"); break; }
+    if (d_count.reserve(s, 1) != hipSuccess || d_keys.reserve(s, rows) != hipSuccess ||
+        d_rows.reserve(s, rows) != hipSuccess) { rc = fail(e, ZB_ENOMEM, "read_instances buffers"); break; }
     if (hipMemsetAsync(d_count, 0, 4, e->stream) != hipSuccess) { rc = ZB_EDEVICE; break; }
     LiveParams lp{};
     lp.rmeta = e->rmeta; lp.rkeys = e->rkeys; lp.rows = rows; lp.count = d_count; lp.cap = rows;
@@ -4520,18 +4311,18 @@ int zb_read_instances(zb_engine* e, uint8_t* buf, size_t cap, size_t* len, uint6
     std::vector<uint32_t> sorted_rows(live);
     for (uint32_t i = 0; i < live; i++) sorted_rows[i] = rws[ord[i]];
     if (hipMemcpy(d_rows, sorted_rows.data(), live * 4, hipMemcpyHostToDevice) != hipSuccess) { rc = ZB_EDEVICE; break; }
-    if (hipMalloc(&d_descs, live * sizeof(zb_rec)) != hipSuccess || hipMalloc(&d_heads, live * sizeof(InstHead)) != hipSuccess ||
-        hipMalloc(&d_len, (live + 1) * 8) != hipSuccess || hipMalloc(&d_off, (live + 1) * 8) != hipSuccess ||
-        hipMalloc(&d_hdrs, live * sizeof(zb_record_header)) != hipSuccess) { rc = fail(e, ZB_ENOMEM, "read_instances"); break; }
+    if (d_descs.reserve(s, live) != hipSuccess || d_heads.reserve(s, live) != hipSuccess ||
+        d_len.reserve(s, live + 1) != hipSuccess || d_off.reserve(s, live + 1) != hipSuccess ||
+        d_hdrs.reserve(s, live) != hipSuccess) { rc = fail(e, ZB_ENOMEM, "read_instances"); break; }
     lp.n = live; lp.descs = d_descs; lp.heads = d_heads;
     launch_row_descs(lp, e->stream);
     // values: the serializer over the descriptors (size pass, scan, write pass)
     SerParams sp{};
-    sp.log = d_descs; sp.arena = e->arena; sp.arena_bytes = e->cfg.arena_bytes; sp.elems = e->d_elems.p; sp.wfs = e->d_wfs.p;
-    sp.queries = e->d_queries.p; sp.pool = e->d_pool.p; sp.ranges = nullptr; sp.nranges = 0;
+    sp.log = d_descs; sp.arena = e->arena; sp.arena_bytes = e->cfg.arena_bytes; sp.elems = e->d_elems; sp.wfs = e->d_wfs;
+    sp.queries = e->d_queries; sp.pool = e->d_pool; sp.ranges = nullptr; sp.nranges = 0;
     sp.cmd_pool = nullptr; sp.start = 0; sp.count = live;
     SerParams sz = sp;
-    sz.lengths = (uint32_t*)d_off;
+    sz.lengths = (uint32_t*)d_off.get();
     launch_ser_size(sz, e->stream);
     std::vector<uint32_t> lens(live);
     if (hipMemcpyAsync(lens.data(), d_off, live * 4, hipMemcpyDeviceToHost, e->stream) != hipSuccess ||
@@ -4541,7 +4332,7 @@ int zb_read_instances(zb_engine* e, uint8_t* buf, size_t cap, size_t* len, uint6
     const uint64_t total = offs[live];
     *len = (size_t)(total + (uint64_t)live * sizeof(InstHead));
     if (!buf || cap < *len) { rc = ZB_ENOMEM; break; }
-    if (hipMalloc(&d_out, total + 1) != hipSuccess ||
+    if (d_out.reserve(s, total + 1) != hipSuccess ||
         hipMemcpy(d_len, offs.data(), (live + 1) * 8, hipMemcpyHostToDevice) != hipSuccess) { rc = ZB_ENOMEM; break; }
     SerParams wr = sp;
     wr.offsets = d_len; wr.out = d_out; wr.headers = d_hdrs;
@@ -4561,7 +4352,6 @@ int zb_read_instances(zb_engine* e, uint8_t* buf, size_t cap, size_t* len, uint6
       o += lens[i];
     }
   } while (0);
-  cleanup();
   return rc;
 }
 
@@ -4628,11 +4418,11 @@ int zb_snapshot(zb_engine* e, uint8_t* buf, size_t cap, size_t* len) {
   // live job states: collected on the device (the table itself is sized by capacity)
   if (e->jobs.keys) {
     const uint64_t slots = e->jobs.mask + 1;
-    rc = grow(e, &e->c_scratch, &e->c_scratch_cap, slots * (sizeof(int64_t) + 1));
+    rc = reserve(e, e->c_scratch, slots * (sizeof(int64_t) + 1), GROW_QUARTER);
     if (rc != ZB_OK) return rc;
-    if (!e->c_count) HIPCHECK(e, hipMalloc(&e->c_count, sizeof(uint32_t)));
+    HIPCHECK(e, e->c_count.reserve(e->stream, 1));
     HIPCHECK(e, hipMemsetAsync(e->c_count, 0, sizeof(uint32_t), e->stream));
-    launch_job_collect(e->jobs, (int64_t*)e->c_scratch, e->c_scratch + slots * sizeof(int64_t), e->c_count, e->stream);
+    launch_job_collect(e->jobs, (int64_t*)e->c_scratch.get(), e->c_scratch + slots * sizeof(int64_t), e->c_count, e->stream);
     uint32_t n = 0;
     HIPCHECK(e, hipMemcpyAsync(&n, e->c_count, sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
     HIPCHECK(e, hipStreamSynchronize(e->stream));
@@ -4699,11 +4489,11 @@ int zb_restore(zb_engine* e, const uint8_t* buf, size_t len) {
     launch_row_relink(c, e->stream);
   }
   if (h.jobs) {
-    rc = grow(e, &e->c_scratch, &e->c_scratch_cap, h.jobs * (sizeof(int64_t) + 1));
+    rc = reserve(e, e->c_scratch, h.jobs * (sizeof(int64_t) + 1), GROW_QUARTER);
     if (rc != ZB_OK) return rc;
     ok = put(e->c_scratch, h.jobs * sizeof(int64_t)) && put(e->c_scratch + h.jobs * sizeof(int64_t), h.jobs);
     if (!ok) return fail(e, ZB_EDEVICE, "restore copy (job states)");
-    launch_job_fill(e->jobs, (const int64_t*)e->c_scratch, e->c_scratch + h.jobs * sizeof(int64_t), (uint32_t)h.jobs,
+    launch_job_fill(e->jobs, (const int64_t*)e->c_scratch.get(), e->c_scratch + h.jobs * sizeof(int64_t), (uint32_t)h.jobs,
                     e->derr, e->stream);
   }
   if (h.sub_count || h.msg_count) {

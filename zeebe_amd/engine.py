@@ -210,6 +210,8 @@ def lib():
         if hasattr(L, "zb_checked_violations"):  # (the guard-band build only)
             L.zb_checked_violations.restype = ctypes.c_ulonglong
             L.zb_checked_violations.argtypes = [ctypes.POINTER(ctypes.c_ulonglong)]
+            L.zb_checked_live.restype = ctypes.c_size_t
+            L.zb_checked_live.argtypes = [ctypes.c_char_p, ctypes.c_size_t]
         _lib = L
     return _lib
 
@@ -234,6 +236,17 @@ def checked_violations():
     n = ctypes.c_ulonglong(0)
     v = L.zb_checked_violations(ctypes.byref(n))
     return int(v), int(n.value)
+
+
+def checked_live():
+    """(count, allocation sites) of the engine allocations still live in the guard-band build, or None for the
+    product library. With every engine closed the count is what they left behind."""
+    L = lib()
+    if not hasattr(L, "zb_checked_live"):
+        return None
+    buf = ctypes.create_string_buffer(1 << 16)
+    n = L.zb_checked_live(buf, len(buf))
+    return int(n), buf.value.decode("utf-8", "replace").split("\n")[:-1]
 
 
 def validate_deployment(xml):
